@@ -1,8 +1,13 @@
 """Benchmark of the BASELINE.json metric: images/sec of the 'unet' training hot path at B=16
 3x256x256 bf16 per GPU on 1..8 MI355X (weak scaling: per-GPU batch fixed).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times exactly K steps and prints the headline line; `--dump-outputs DIR` also writes what
+the last timed step computed as DIR/<name>.npy (same arguments, same inputs: two builds compare output for output).
+Everything else below -- forward+backward replays, sensors, per-kernel profile and roofline, fp32 mode, second
+headline, CPU baseline, stock-PyTorch yardstick -- runs only with `--full`.
 
 `--gpus N` with N > 1 outside a launcher starts N fresh rank processes itself (unet_zoo_amd.launch, before this
 process makes any GPU call) and relays rank 0's JSON line; with fewer than N visible GPUs it exits non-zero.
@@ -12,9 +17,9 @@ One "step" = the reference's whole training step (unet_zoo/utils/training_loop.p
 zero_grad -> forward -> BCEWithLogits -> backward (-> RCCL gradient all-reduce) ->
 clip_grad_norm_(1.0) -> AdamW.  Inputs are synthetic and already resident in HBM.  `value` is
 images/sec of that WHOLE step (a lower bound of the fwd+bwd rate, which is reported beside it as
-`fwd_bwd_images_per_s`, timed on the forward+backward hipGraph alone).
+`fwd_bwd_images_per_s`, timed on the forward+backward hipGraph alone, --full).  `loss` is the last timed step's.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full):
   roofline     — the dominant kernel (most GPU time), timed live with HIP events on the launch
                  stream during the timed steps; flops/bytes are the algorithmic counts of
                  SURVEY.md §8d for exactly the launches timed.
@@ -283,8 +288,7 @@ def _as_float(o):
 
 
 def time_graphed(gs, x, mask, steps, warmup, distributed, dev):
-    """W untimed + exactly K timed whole steps between barrier + synchronize; returns (max-over-ranks seconds,
-    seconds of K forward+backward(+all-reduce) replays alone)"""
+    """W untimed + exactly K timed whole steps between barrier + synchronize; returns max-over-ranks seconds"""
     for _ in range(max(warmup, 1)):      # the first call dry-runs, lays out the flat buffers and captures
         gs(x, mask)
     if distributed:
@@ -301,12 +305,60 @@ def time_graphed(gs, x, mask, steps, warmup, distributed, dev):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    return elapsed
+
+
+def time_fwd_bwd(gs, x, mask, steps):
+    """seconds of K forward+backward(+all-reduce) replays alone (no optimizer step: the parameters stay as they are)"""
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     for _ in range(steps):
         gs.forward_backward(x, mask)
     torch.cuda.synchronize()
-    return elapsed, time.perf_counter() - t1
+    return time.perf_counter() - t1
+
+
+DUMP_BUDGET_ELEMS = 15_000_000       # float32 elements over all dumped arrays: 60 MB, under the 64 MB bound
+
+
+def dump_outputs(out_dir: str, arrays) -> None:
+    """Write (name, tensor) pairs as out_dir/<name>.npy in float32.  An array longer than its share of the budget is
+    replaced by a fixed sample of its flattened elements: sorted indices from a generator seeded by 0, so the same
+    length gives the same sample in every run and every build."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BUDGET_ELEMS // max(len(arrays), 1)
+    for name, t in arrays:
+        flat = t.detach().reshape(-1).float()
+        if flat.numel() > cap:
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), flat.cpu().numpy().astype(np.float32).reshape(
+            tuple(t.shape) if flat.numel() == t.numel() else (-1,)))
+
+
+def step_outputs(outputs, loss, dice, model) -> list:
+    """What a caller of the training step receives after its last call, as (name, tensor) pairs: the model's outputs
+    (a dict or list of heads: one array per head), the loss and Dice scalars, and the updated parameters, their
+    gradients and the floating-point buffers (BatchNorm running statistics), each concatenated in the model's order."""
+    arrays = []
+    if isinstance(outputs, dict):
+        arrays += [(f"outputs_{k}", v) for k, v in outputs.items()]
+    elif isinstance(outputs, (list, tuple)):
+        arrays += [(f"outputs_{i}", v) for i, v in enumerate(outputs)]
+    else:
+        arrays.append(("outputs", outputs))
+    arrays.append(("loss", loss.reshape(1)))
+    if dice is not None:
+        arrays.append(("dice", dice.reshape(1)))
+    params = list(model.parameters())
+    arrays.append(("parameters", torch.cat([p.detach().reshape(-1).float() for p in params])))
+    arrays.append(("gradients", torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                                           for p in params])))
+    bufs = [b.detach().reshape(-1).float() for b in model.buffers() if b.is_floating_point()]
+    if bufs:
+        arrays.append(("buffers", torch.cat(bufs)))
+    return arrays
 
 
 def second_headline(dev, steps: int, warmup: int, cpu_steps: int, with_cpu: bool, loss_impl: str):
@@ -321,7 +373,8 @@ def second_headline(dev, steps: int, warmup: int, cpu_steps: int, with_cpu: bool
     x = torch.randn(B, 3, hw, hw, generator=g).to(dev)
     mask = (torch.rand(B, 1, hw, hw, generator=g) > 0.5).float().to(dev)
     gs = GraphedStep(m, "bce_dice" if loss_impl == "hip" else torch_criterion, lr=1e-4, weight_decay=1e-5, max_norm=1.0)
-    elapsed, fb_s = time_graphed(gs, x, mask, steps, warmup, False, dev)
+    elapsed = time_graphed(gs, x, mask, steps, warmup, False, dev)
+    fb_s = time_fwd_bwd(gs, x, mask, steps)
     out = {"metric": f"images/sec (fwd+bwd) {name} B={B} 3x{hw}x{hw} (window {kw['window_size']}), 1 MI355X",
            "value": round(B * steps / elapsed, 2), "unit": "images/sec", "ms_per_step": round(elapsed / steps * 1e3, 3),
            "steps": steps, "warmup": warmup, "dtype": "bf16", "data": "synthetic",
@@ -389,7 +442,18 @@ def main():
     ap.add_argument("--fp32-steps", type=int, default=10,
                     help="N=1, bf16 runs: also time this many steps of the SAME model in the fp32 run mode (the "
                          "mode that meets the 1e-3 parity bound) and report fp32_images_per_s; 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: forward+backward replays, the loss re-check, device sensors and the MFMA "
+                         "clock probe, the per-kernel profile steps and roofline, the fp32 run mode, the second headline, the "
+                         "CPU baseline and the stock-PyTorch yardstick (each as its own option above selects)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (outputs, loss, Dice, and a fixed "
+                         "sample of the parameters, gradients and buffers) as DIR/<name>.npy, float32, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.torch_baseline and not (args.full or args.torch_baseline_child):
+        ap.error("--torch-baseline is part of --full")
     global _LOSS_IMPL
     _LOSS_IMPL = args.loss
 
@@ -423,7 +487,7 @@ def main():
         return
     helper = None
     want_yardstick = args.torch_baseline or not (args.no_torch_baseline or args.no_cpu_baseline)
-    if (want_yardstick and not launch.under_launcher() and (args.gpus in (None, 1)) and not args.force_dist):
+    if (args.full and want_yardstick and not launch.under_launcher() and (args.gpus in (None, 1)) and not args.force_dist):
         import subprocess
         import tempfile
         helper_out = os.path.join(tempfile.mkdtemp(prefix="uz_bench_"), "torch_baseline.json")
@@ -498,6 +562,7 @@ def _bench_main(args, helper, helper_out):
     mask = (torch.rand(args.batch, 1, args.size, args.size, generator=g) > 0.5).float().to(dev)
 
     fb_events = []
+    last_out = {}
     net = model
     opt = None
 
@@ -507,7 +572,8 @@ def _bench_main(args, helper, helper_out):
         if timed:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        loss = model_loss(net(x), mask)
+        out = last_out["outputs"] = net(x)
+        loss = model_loss(out, mask)
         loss.backward()
         if timed:
             e1.record()
@@ -520,7 +586,7 @@ def _bench_main(args, helper, helper_out):
     comm_tuning = None
     fb_graph_ms = None
     loss_recheck = None
-    dev_before = device_state(dev.index or 0) if rank == 0 else None
+    dev_before = device_state(dev.index or 0) if rank == 0 and args.full else None
     if args.graph == "on":
         gs = GraphedStep(model, "bce_dice" if args.loss == "hip" else torch_criterion, lr=1e-4, weight_decay=1e-5,
                          max_norm=1.0, phases=args.phases, data_parallel=distributed, cu_reserve=args.cu_reserve,
@@ -532,14 +598,17 @@ def _bench_main(args, helper, helper_out):
             comm_tuning = gs.autotune_comm(x, mask)
             comm_tuning = {k: round(v, 3) for k, v in comm_tuning.items()}
             comm_tuning["chosen"] = gs.comm
-        elapsed, fb_s = time_graphed(gs, x, mask, args.steps, args.warmup, distributed, dev)
-        fb_graph_ms = fb_s / args.steps * 1e3
+        elapsed = time_graphed(gs, x, mask, args.steps, args.warmup, distributed, dev)
         launch_mode = gs.describe()
-        # the loss comes straight out of the replayed graph (uz_bce_dice: no library reduction, no memset node);
-        # re-evaluated eagerly from the same replay's logits it must be the same number
         final_loss = float(gs.loss.item())
-        with torch.no_grad():
-            loss_recheck = float(torch_criterion(gs.outputs, mask).item())
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, step_outputs(gs.outputs, gs.loss, gs.dice, model))
+        if args.full:
+            # the loss comes straight out of the replayed graph (uz_bce_dice: no library reduction, no memset node);
+            # re-evaluated eagerly from the same replay's logits it must be the same number
+            with torch.no_grad():
+                loss_recheck = float(torch_criterion(gs.outputs, mask).item())
+            fb_graph_ms = time_fwd_bwd(gs, x, mask, args.steps) / args.steps * 1e3
     else:
         if distributed:
             net = RcclDataParallel(model)
@@ -562,6 +631,32 @@ def _bench_main(args, helper, helper_out):
             elapsed = t.item()
         final_loss = float(loss.item())
         launch_mode = "eager launches (autograd node + torch clip_grad_norm_ + fused AdamW)"
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, step_outputs(last_out["outputs"], loss, None, model))
+
+    if rank == 0:
+        ms = elapsed / args.steps * 1e3
+        line = {
+            "metric": "images/sec (fwd+bwd) at B=16 3x256x256, 1/2/4/8 MI355X" if (args.model, args.size, args.batch) == ("unet", 256, 16)
+                      else f"images/sec (fwd+bwd) {args.model} B={args.batch} 3x{args.size}x{args.size}",
+            "value": round(world * args.batch * args.steps / elapsed, 2), "unit": "images/sec", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": f"{args.model} train step (zero_grad+fwd+BCE+bwd+clip+AdamW), B={args.batch}/GPU "
+                                   f"3x{args.size}x{args.size}, random-init weights",
+                       "global_batch": world * args.batch, "parallelism": f"dp{world}"},
+            "loss": round(final_loss, 5),
+            "launch": launch_mode,
+            "cu_reserve": L.get_cu_reserve(),
+            "comm_tuning_ms": comm_tuning if args.graph == "on" else None,
+            "comm_dtype": args.comm_dtype if distributed else None,
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if distributed:
+            dist.destroy_process_group()
+        return
 
     dev_after = device_state(dev.index or 0) if rank == 0 else None
     # per-launch HIP events (same process, same shapes, eager launches right after the timed steps)
@@ -589,7 +684,7 @@ def _bench_main(args, helper, helper_out):
         m32.run_dtype = torch.float32
         m32 = m32.to(dev).train()
         gs32 = GraphedStep(m32, "bce_dice" if args.loss == "hip" else torch_criterion, lr=1e-4, weight_decay=1e-5)
-        el32, _ = time_graphed(gs32, x, mask, args.fp32_steps, 2, False, dev)
+        el32 = time_graphed(gs32, x, mask, args.fp32_steps, 2, False, dev)
         fp32 = {"fp32_images_per_s": round(args.batch * args.fp32_steps / el32, 2),
                 "fp32_ms_per_step": round(el32 / args.fp32_steps * 1e3, 3), "fp32_steps": args.fp32_steps,
                 "fp32_loss": round(float(gs32.loss.item()), 5)}
@@ -602,8 +697,6 @@ def _bench_main(args, helper, helper_out):
         except Exception as e:                   # noqa: BLE001
             mfma_clock = {"error": repr(e)[:120]}
     if rank == 0:
-        ms = elapsed / args.steps * 1e3
-        value = world * args.batch * args.steps / elapsed
         if fb_graph_ms is not None:
             fb_ms = fb_graph_ms
         else:
@@ -658,27 +751,14 @@ def _bench_main(args, helper, helper_out):
             roofline.update({"families": sorted(dom["families"]), "launches_per_step": dom["launches"] // nprof,
                              "avg_launch_us": round(sec_per_launch * 1e6, 2),
                              "share_of_step": round(dom["ms"] / nprof / ms, 4)})
-        line = {
-            "metric": "images/sec (fwd+bwd) at B=16 3x256x256, 1/2/4/8 MI355X" if (args.model, args.size, args.batch) == ("unet", 256, 16)
-                      else f"images/sec (fwd+bwd) {args.model} B={args.batch} 3x{args.size}x{args.size}",
-            "value": round(value, 2), "unit": "images/sec", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": f"{args.model} train step (zero_grad+fwd+BCE+bwd+clip+AdamW), B={args.batch}/GPU "
-                                   f"3x{args.size}x{args.size}, random-init weights",
-                       "global_batch": world * args.batch, "parallelism": f"dp{world}"},
+        line.update({
             "fwd_bwd_ms": round(fb_ms, 3) if fb_ms else None,
             "fwd_bwd_images_per_s": round(args.batch * world / (fb_ms * 1e-3), 2) if fb_ms else None,
-            "loss": round(final_loss, 5),
             "loss_eager_recheck": round(loss_recheck, 5) if loss_recheck is not None else None,
             "roofline": roofline,
-            "launch": launch_mode,
-            "cu_reserve": L.get_cu_reserve(),
-            "comm_tuning_ms": comm_tuning if args.graph == "on" else None,
-            "comm_dtype": args.comm_dtype if distributed else None,
             "device": {"before_timed_steps": dev_before, "after_timed_steps": dev_after, "mfma_clock": mfma_clock},
             "kernel_ms_per_step": {k: round(v["ms"] / nprof, 3) for k, v in sorted(prof.items())},
-        }
+        })
         # the north star's block-level line: unet level 1 DoubleConv forward (im2col + both convolutions + BatchNorm
         # finalize / apply + ReLU + pool) as the eager profile steps timed it, against SURVEY 8d's floor
         # 4 * P * Cin + s * P * 3 * Cout + weights (415 MB at B = 16 256 x 256 bf16) and 8 TB/s

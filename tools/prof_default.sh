@@ -1,26 +1,28 @@
 #!/bin/bash
 # rocprofv3 --kernel-trace --stats of the DEFAULT bench command (graph replays + the eager, event-bracketed profile steps)
 # and the dominant kernel family's average duration in each part of the trace beside the bench line's own figure.
-# usage (on the GPU box): bash tools/prof_default.sh  -> gpurun_out/prof_default_bench.json, gpurun_out/prof_default_kernel_stats.csv
+# usage (on an MI355X): bash tools/prof_default.sh  -> $OUT/prof_default_bench.json, $OUT/prof_default_kernel_stats.csv
+# (OUT: the output directory, default out/)
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-rm -rf gpurun_out/prof_default; mkdir -p gpurun_out/prof_default
+export OUT=${OUT:-out}
+rm -rf $OUT/prof_default; mkdir -p $OUT/prof_default
 # the same command WITHOUT the profiler first: its per-launch figure is the one the bench line carries
-python3 bench.py --no-cpu-baseline --fp32-steps 0 --second-steps 0 > gpurun_out/prof_default_bench_plain.json 2> gpurun_out/prof_default/plain_err.log
-rocprofv3 --kernel-trace --stats -d gpurun_out/prof_default -o x -- python3 bench.py --no-cpu-baseline --fp32-steps 0 --second-steps 0 > gpurun_out/prof_default_bench.json 2> gpurun_out/prof_default/err.log
-DB=$(ls gpurun_out/prof_default/*.db gpurun_out/prof_default/*/*.db 2>/dev/null | head -1)
-python3 tools/prof_csv.py "$DB" "rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --fp32-steps 0 --second-steps 0" > gpurun_out/prof_default_kernel_stats.csv
+python3 bench.py --full --no-cpu-baseline --fp32-steps 0 --second-steps 0 > $OUT/prof_default_bench_plain.json 2> $OUT/prof_default/plain_err.log
+rocprofv3 --kernel-trace --stats -d $OUT/prof_default -o x -- python3 bench.py --full --no-cpu-baseline --fp32-steps 0 --second-steps 0 > $OUT/prof_default_bench.json 2> $OUT/prof_default/err.log
+DB=$(ls $OUT/prof_default/*.db $OUT/prof_default/*/*.db 2>/dev/null | head -1)
+python3 tools/prof_csv.py "$DB" "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --fp32-steps 0 --second-steps 0" > $OUT/prof_default_kernel_stats.csv
 python3 - <<'PY'
-import sqlite3, glob, json
-db = glob.glob("gpurun_out/prof_default/*.db") + glob.glob("gpurun_out/prof_default/*/*.db")
+import sqlite3, glob, json, os
+db = glob.glob(os.environ["OUT"] + "/prof_default/*.db") + glob.glob(os.environ["OUT"] + "/prof_default/*/*.db")
 c = sqlite3.connect(db[0])
-d = json.loads(open("gpurun_out/prof_default_bench.json").read().strip().splitlines()[-1])
+d = json.loads(open(os.environ["OUT"] + "/prof_default_bench.json").read().strip().splitlines()[-1])
 # the kernel the un-profiled bench line names (under the profiler the two-kernel operations -- weight gradient + slab
 # reduction inside one event bracket -- read longer and can take over the top place; the comparison below is about the
 # convolution either way).  A kernel = one ping-pong configuration with both of its epilogue variants, as bench.py groups them.
 import importlib.util
 spec = importlib.util.spec_from_file_location("bench_mod", "bench.py")
 bm = importlib.util.module_from_spec(spec); spec.loader.exec_module(bm)
-plain = json.loads(open("gpurun_out/prof_default_bench_plain.json").read().strip().splitlines()[-1])
+plain = json.loads(open(os.environ["OUT"] + "/prof_default_bench_plain.json").read().strip().splitlines()[-1])
 fam = plain["roofline"]["kernel"]             # the dominant kernel family of the un-profiled line, by the library's own name
 pats = bm.PMC_KEYS[fam]                       # ... and the kernel symbols that belong to it (bench.py's table)
 rows = []
@@ -42,7 +44,7 @@ print("eager profile steps in the trace: avg %.2f us" % (sum(r[1] for r in eager
 print("bench.py per-launch figure from its own HIP events, same run: %.2f us   ms_per_step %.3f (under the profiler)" % (ev_us, d["ms_per_step"]))
 a = sum(r[1] for r in replays) / len(replays)
 print("eager-event figure vs graph replay, both under the profiler: %+.1f %%" % ((ev_us / a - 1) * 100))
-pl = json.loads(open("gpurun_out/prof_default_bench_plain.json").read().strip().splitlines()[-1])
+pl = json.loads(open(os.environ["OUT"] + "/prof_default_bench_plain.json").read().strip().splitlines()[-1])
 r = pl["roofline"]
 print("the same command without the profiler, same box: roofline.kernel %s avg_launch_us %.2f frac %.4f ms_per_step %.3f" % (r["kernel"], r["avg_launch_us"], r["frac"], pl["ms_per_step"]))
 print("un-profiled eager-event figure vs the graph replays of the trace: %+.1f %%" % ((r["avg_launch_us"] / a - 1) * 100))

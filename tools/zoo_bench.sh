@@ -6,7 +6,7 @@ mkdir -p gpurun_out/r05
 for spec in $1; do
   IFS=: read m s b nb <<< "$spec"
   tb="--torch-baseline"; [ -n "$nb" ] && tb=""
-  timeout -k 10 420 python3 bench.py --model $m --size $s --batch $b --steps 20 --warmup 5 --no-cpu-baseline --second-steps 0 \
+  timeout -k 10 420 python3 bench.py --full --model $m --size $s --batch $b --steps 20 --warmup 5 --no-cpu-baseline --second-steps 0 \
     --fp32-steps 0 $tb > gpurun_out/r05/zoo_${m}_${s}.json 2> gpurun_out/r05/zoo_${m}_${s}.err
   python3 - gpurun_out/r05/zoo_${m}_${s}.json <<'PY'
 import json, sys
