@@ -647,12 +647,16 @@ int uz_dwconv3x3_wgrad(int dtype, const void* x, int ldx, const void* g, int ldg
  * (EfficientSelfAtten.sr, missformer.py:17-18,26-27) as GEMM rows; inverse != 0 scatters such rows back. */
 int uz_space_to_depth(int dtype, const void* src, int lds, void* dst, int ldd, int N, int Ho, int Wo, int C, int r,
                       int inverse, void* stream);
+/* the same over an H x W fine map with Ho = H / r, Wo = W / r rounded down (Conv2d drops the bottom / right border when
+ * r does not divide the map, unext.py Attention.sr); inverse != 0 also writes zeros to that border. */
+int uz_space_to_depth_crop(int dtype, const void* src, int lds, void* dst, int ldd, int N, int H, int W, int C, int r,
+                           int inverse, void* stream);
 /* im2col of the NCHW fp32 input for OverlapPatchEmbeddings' Conv2d(3, 64, 7, 4, 3) (missformer.py:242,312):
  * out[(n, ho, wo)][(kh*k + kw)*C + c] in the run dtype, zero beyond k*k*C up to Kpad. */
 int uz_im2col_nchw(int dtype, const float* x_nchw, int N, int C, int H, int W, int k, int stride, int pad, int Kpad,
                    void* out, void* stream);
-/* softmax(q k^T * scale) v per (image, head), head_dim 64 (missformer.py:21-39, :113-128).
- * q / out: (B*N, ld) token tensors, head h in columns [64h, 64h+64).  Key j of image b is row
+/* softmax(q k^T * scale) v per (image, head), head_dim D a multiple of 8 in [8, 128] (missformer.py:21-39, :113-128;
+ * unext.py Attention).  q / out: (B*N, ld) token tensors, head h in columns [D*h, D*h+D).  Key j of image b is row
  * ((j / kps) * B + b) * kps + j % kps of k / v (kps = NK: one [B][NK] block; the bridge attends to four
  * blocks of kps rows, missformer.py:81-100).  lse: B*heads*N floats kept for the backward: log2 of the sum of
  * exp(scaled scores), i.e. logsumexp / ln 2. */
@@ -664,8 +668,8 @@ typedef struct uz_sra_desc {
 int uz_sra_fwd(const uz_sra_desc* d, const void* q, const void* k, const void* v, void* out, float* lse,
                void* stream);
 long long uz_sra_bwd_workspace_bytes(const uz_sra_desc* d);
-/* go = d(loss)/d(out); dq like q; dkv: dense (B*NK, 2*heads*64) rows laid out like the kv tensor, dK in the
- * first heads*64 columns and dV in the rest (k = kv, v = kv + heads*64, ldk = ldv = 2*heads*64). */
+/* go = d(loss)/d(out); dq like q; dkv: dense (B*NK, 2*heads*D) rows laid out like the kv tensor, dK in the
+ * first heads*D columns and dV in the rest (k = kv, v = kv + heads*D, ldk = ldv = 2*heads*D). */
 int uz_sra_bwd(const uz_sra_desc* d, const void* q, const void* k, const void* v, const void* o, const float* lse,
                const void* go, int ldgo, void* dq, int lddq, void* dkv, int lddkv, void* workspace, void* stream);
 

@@ -45,7 +45,7 @@ EXPORTS = (
     "uz_cpb_fwd_batched", "uz_cpb_bwd_batched_workspace_bytes", "uz_cpb_bwd_batched",
     "uz_clip_adamw_workspace_bytes", "uz_clip_adamw",
     "uz_gelu_fwd", "uz_gelu_bwd", "uz_dwconv3x3", "uz_dwconv3x3_wgrad_rows", "uz_dwconv3x3_wgrad",
-    "uz_space_to_depth", "uz_im2col_nchw", "uz_sra_fwd", "uz_sra_bwd_workspace_bytes", "uz_sra_bwd",
+    "uz_space_to_depth", "uz_space_to_depth_crop", "uz_im2col_nchw", "uz_sra_fwd", "uz_sra_bwd_workspace_bytes", "uz_sra_bwd",
     "uz_bce_dice_workspace_bytes", "uz_bce_dice", "uz_colsum_batched_workspace_bytes", "uz_colsum_batched", "uz_sum_rows_f32_batched", "uz_conv_igemm_res", "uz_wgrad_multi_workspace_bytes", "uz_wgrad_multi", "uz_conv_igemm_res_ws",
     "uz_add_relu", "uz_relu_bwd", "uz_pil_resample_h_u8", "uz_pil_resample_v_f32",
     "uz_gemm_nt", "uz_softmax_fwd", "uz_softmax_bwd", "uz_adaptive_avgpool_fwd", "uz_adaptive_avgpool_bwd",
@@ -263,6 +263,7 @@ def load():
     lib.uz_dwconv3x3_wgrad_rows.argtypes = [ip, ip, ip, ip, ip]
     lib.uz_dwconv3x3_wgrad.argtypes = [ip, vp, ip, vp, ip, vp, ip, ip, ip, ip, vp]
     lib.uz_space_to_depth.argtypes = [ip, vp, ip, vp, ip, ip, ip, ip, ip, ip, ip, vp]
+    lib.uz_space_to_depth_crop.argtypes = [ip, vp, ip, vp, ip, ip, ip, ip, ip, ip, ip, vp]
     lib.uz_im2col_nchw.argtypes = [ip, vp, ip, ip, ip, ip, ip, ip, ip, ip, vp, vp]
     lib.uz_sra_fwd.argtypes = [POINTER(SraDesc), vp, vp, vp, vp, vp, vp]
     lib.uz_sra_bwd_workspace_bytes.argtypes = [POINTER(SraDesc)]

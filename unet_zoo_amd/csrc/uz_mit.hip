@@ -1,5 +1,5 @@
 // MISSFormer / MiT blocks for gfx950 (reference unet_zoo/models/missformer.py):
-//   * spatial-reduction attention  softmax(q k^T * scale) v  with head_dim 64, N queries against NK << N reduced
+//   * spatial-reduction attention  softmax(q k^T * scale) v  with head_dim D (multiples of 8 up to 128), N queries against NK << N reduced
 //     keys per image (EfficientSelfAtten :21-39, M_EfficientSelfAtten :113-128): forward, dQ and dK/dV kernels on
 //     v_mfma_f32_32x32x16_bf16 (bf16) and a scalar fp32 path for the fp32 run mode;
 //   * depthwise 3x3 convolution of MixFFN_skip (DWConv :168-177, "dwconv(fc1) + fc1" :205) forward / input
@@ -252,27 +252,36 @@ __global__ __launch_bounds__(256) void dwconv3x3_wgrad_kernel(const T* __restric
 }
 
 // ---------------------------------------------------------------------------------------------
-// space-to-depth: d[n, ho, wo, (ty*r + tx)*C + c] = s[n, ho*r + ty, wo*r + tx, c]   (inverse: the same
-// index map with source and destination exchanged)
+// space-to-depth: d[n, ho, wo, (ty*r + tx)*C + c] = s[n, ho*r + ty, wo*r + tx, c] over the H x W fine map, Ho = H / r,
+// Wo = W / r (floor: a Conv2d(C, C', r, r) drops the bottom / right border when r does not divide the map).  Inverse:
+// the same index map with source and destination exchanged, and zeros written to the dropped border.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void space_to_depth_kernel(const T* __restrict__ src, int lds_, T* __restrict__ dst,
-                                                             int ldd, int N, int Ho, int Wo, int C, int r, int inverse) {
+                                                             int ldd, int N, int H, int W, int C, int r, int inverse) {
   constexpr int VEC = ElemTraits<T>::VEC;
-  const int CC = C / VEC;
-  const long long total = (long long)N * Ho * r * Wo * r * CC;
+  const int CC = C / VEC, Ho = H / r, Wo = W / r;
+  const long long total = (long long)N * H * W * CC;
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
        idx += (long long)gridDim.x * blockDim.x) {
     const int c0 = (int)(idx % CC) * VEC;
     long long u = idx / CC;
-    const int w = (int)(u % (Wo * r));
-    u /= Wo * r;
-    const int h = (int)(u % (Ho * r)), n = (int)(u / (Ho * r));
-    const size_t fine = (((size_t)n * Ho * r + h) * Wo * r + w);
-    const size_t coarse = (((size_t)n * Ho + h / r) * Wo + w / r);
+    const int w = (int)(u % W);
+    u /= W;
+    const int h = (int)(u % H), n = (int)(u / H);
+    const bool kept = h < Ho * r && w < Wo * r;
+    const size_t fine = ((size_t)n * H + h) * W + w;
+    const size_t coarse = ((size_t)n * Ho + (kept ? h / r : 0)) * Wo + (kept ? w / r : 0);
     const int tap = (h % r) * r + (w % r);
-    if (inverse) st16(dst + fine * ldd + c0, ld16(src + coarse * lds_ + (size_t)tap * C + c0));
-    else st16(dst + coarse * ldd + (size_t)tap * C + c0, ld16(src + fine * lds_ + c0));
+    if (inverse) {
+      const Vec16<T> v = ld16(src + coarse * lds_ + (size_t)(kept ? tap : 0) * C + c0);
+      Vec16<T> z;
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) z.v[i] = kept ? v.v[i] : (T)0.f;
+      st16(dst + fine * ldd + c0, z);
+    } else if (kept) {
+      st16(dst + coarse * ldd + (size_t)tap * C + c0, ld16(src + fine * lds_ + c0));
+    }
   }
 }
 
@@ -314,24 +323,35 @@ __global__ __launch_bounds__(256) void sum_parts_kernel(const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
-// Spatial-reduction attention.  q [B][N][ldq], head h = columns h*64 .. h*64+63; keys and values are rows of
-// the kv tensor: key j of image b is row ((j / kps) * B + b) * kps + j % kps  (kps = NK for one [B][NK] block;
-// the bridge's keys are four blocks of kps rows, one per scale, each stored [B][kps]).  lse is kept in
-// log2 units of the scaled scores: p = exp2(s * scale * log2(e) - lse).
+// Spatial-reduction attention.  q [B][N][ldq], head h = columns h*D .. h*D+D-1 (D = head_dim, a multiple of 8 in
+// [8, 128]); keys and values are rows of the kv tensor: key j of image b is row ((j / kps) * B + b) * kps + j % kps
+// (kps = NK for one [B][NK] block; the bridge's keys are four blocks of kps rows, one per scale, each stored
+// [B][kps]).  lse is kept in log2 units of the scaled scores: p = exp2(s * scale * log2(e) - lse).
+// The kernels are templated on T = ceil(D / 32), the number of 32-wide d tiles; D itself is a run-time mask.  Columns
+// [D, 32T) are zero in the LDS tiles and in the operand registers, so QK^T contracts over D padded to 16 and the padded
+// rows of PV / dV^T / dK^T are computed and never stored.  T = 2, D = 64 runs MISSFormer's arithmetic unchanged.
 // ---------------------------------------------------------------------------------------------
 struct SraArgs {
   const void *q, *k, *v, *o, *go;   // go: gradient of o (backward)
   void *out, *dq;                   // forward output / dQ
   float *lse, *delta, *ws;          // [B][heads][N] each; ws: dK/dV partials [chunk][kv rows][ldws]
-  int B, N, NK, heads, kps;
+  int B, N, NK, heads, kps, D;
   int ldq, ldk, ldv, ldo, ldgo, lddq, ldws;
   int qc;                            // queries per chunk of the dK/dV kernel
   long long ws_chunk;                // floats per chunk of ws
   float scale;
 };
 
-constexpr int SD = 64;   // head dim
-constexpr int TS = 72;   // LDS row stride in bf16 elements (144 B: 16-byte row reads of 16 lanes hit 16 distinct bank quads)
+constexpr int SD_MIN = 8, SD_MAX = 128;   // supported head dims: multiples of 8 in [SD_MIN, SD_MAX]
+
+// Shapes per T.  TS: LDS row stride in bf16 elements, 32T + 8 = 64T + 16 bytes = 4T + 1 sixteen-byte bank quads -- odd,
+// so the 16-byte row reads of 16 lanes (16 consecutive rows) hit 16 distinct quads (T = 2: 72 elements, 144 B).
+template <int T> struct SraShape {
+  static constexpr int TS = 32 * T + 8;
+  static constexpr int NS = 2 * T;                  // 16-wide contraction slices of QK^T
+  static constexpr int CPR = 4 * T;                 // 16-byte chunks per staged row
+  static constexpr int CPT = (CPR + 7) / 8;         // ... per staging thread (eight threads per row)
+};
 
 __device__ __forceinline__ size_t kv_row(const SraArgs& a, int b, int j) {
   return ((size_t)(j / a.kps) * a.B + b) * a.kps + j % a.kps;
@@ -345,6 +365,7 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 // the 32x32 accumulator of the previous product holds its rows, so that accumulator feeds the B operand as is.
 // ds_read_b64_tr_b16: a group of 16 lanes reads a 4-row x 16-column block; lane 4q+p supplies the address of row q,
 // columns 4p..4p+3 and lane i receives column i of the four rows.
+template <int TS>
 __device__ __forceinline__ bf16x8 tr_operand(const bf16_t* tile, int row0, int col0, int lane) {
   const int i = lane & 15, cb = col0 + 16 * ((lane >> 4) & 1);
   const bf16_t* p = tile + (row0 + (i >> 2)) * TS + cb + 4 * (i & 3);
@@ -355,18 +376,41 @@ __device__ __forceinline__ bf16x8 tr_operand(const bf16_t* tile, int row0, int c
   return __builtin_bit_cast(bf16x8, both);
 }
 
+template <int TS>
 __device__ __forceinline__ bf16x8 row_operand(const bf16_t* tile, int row, int s, int lh) {
   return *reinterpret_cast<const bf16x8*>(tile + row * TS + 16 * s + 8 * lh);
 }
 
-// B operand rows of this lane's query / key straight from global memory (zero beyond `valid`)
-__device__ __forceinline__ void load_b_operand(const bf16_t* rowp, bool valid, int lh, bf16x8* f) {
+__device__ __forceinline__ uint4 ld_u4(const bf16_t* p) { return *reinterpret_cast<const uint4*>(p); }
+__device__ __forceinline__ uint4 sel_u4(bool ok, const uint4& v) { return ok ? v : make_uint4(0, 0, 0, 0); }
+
+// B operand rows of this lane's query / key straight from global memory: NS slices of 16, zero beyond `valid` and
+// beyond column D.  rowp is a valid row either way; every load issues (clamped column) and the mask is a select.
+template <int NS>
+__device__ __forceinline__ void load_b_operand(const bf16_t* rowp, bool valid, int lh, int D, bf16x8* f) {
+  uint4 raw[NS];
 #pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    if (valid) f[s] = *reinterpret_cast<const bf16x8*>(rowp + 16 * s + 8 * lh);
-    else
+  for (int s = 0; s < NS; ++s) raw[s] = ld_u4(rowp + min(16 * s + 8 * lh, D - 8));
 #pragma unroll
-      for (int e = 0; e < 8; ++e) f[s][e] = (bf16_t)0.f;
+  for (int s = 0; s < NS; ++s) asm volatile("" : "+v"(raw[s].x), "+v"(raw[s].y), "+v"(raw[s].z), "+v"(raw[s].w));
+#pragma unroll
+  for (int s = 0; s < NS; ++s) f[s] = __builtin_bit_cast(bf16x8, sel_u4(valid && 16 * s + 8 * lh < D, raw[s]));
+}
+
+// 32 rows of a key / query block into an LDS tile: raw 16-byte chunks fetched with clamped addresses (fetch_rows), the
+// mask applied where they are stored (stage_rows); columns [D, 32T) are written as zeros.
+template <int T>
+__device__ __forceinline__ void fetch_rows(const bf16_t* rowp, int D, int sch, uint4* r) {
+#pragma unroll
+  for (int i = 0; i < SraShape<T>::CPT; ++i) r[i] = ld_u4(rowp + min(8 * (sch + 8 * i), D - 8));
+}
+template <int T>
+__device__ __forceinline__ void stage_rows(bf16_t* tile, int srow, int sch, bool row_ok, int D, const uint4* r) {
+#pragma unroll
+  for (int i = 0; i < SraShape<T>::CPT; ++i) {
+    const int ch = sch + 8 * i;
+    if (ch < SraShape<T>::CPR)
+      *reinterpret_cast<uint4*>(tile + srow * SraShape<T>::TS + 8 * ch) = sel_u4(row_ok && 8 * ch < D, r[i]);
   }
 }
 
@@ -377,57 +421,61 @@ __device__ __forceinline__ f32x16 zero_acc() {
   return z;
 }
 
-// store a transposed accumulator pair (rows d of two 32-row tiles, column = this lane's token) as token-major bf16
-__device__ __forceinline__ void store_t_tiles(bf16_t* rowp, int lh, const f32x16& t0, const f32x16& t1, float mul) {
+// store transposed accumulators (rows d of T 32-row tiles, column = this lane's token) as token-major bf16, d < D
+template <int T>
+__device__ __forceinline__ void store_t_tiles(bf16_t* rowp, int lh, int D, const f32x16* t, float mul) {
 #pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
+  for (int dt = 0; dt < T; ++dt)
 #pragma unroll
     for (int q4 = 0; q4 < 4; ++q4) {
+      const int col = 32 * dt + 8 * q4 + 4 * lh;
+      if (col >= D) continue;
       bf16x4 o4;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) o4[e] = (bf16_t)((dt ? t1 : t0)[4 * q4 + e] * mul);
-      *reinterpret_cast<bf16x4*>(rowp + 32 * dt + 8 * q4 + 4 * lh) = o4;
+      for (int e = 0; e < 4; ++e) o4[e] = (bf16_t)(t[dt][4 * q4 + e] * mul);
+      *reinterpret_cast<bf16x4*>(rowp + col) = o4;
     }
 }
 
+template <int T>
 __global__ __launch_bounds__(256) void sra_fwd_mfma_kernel(const SraArgs a) {
+  using S = SraShape<T>;
+  constexpr int TS = S::TS, NS = S::NS;
   __shared__ __attribute__((aligned(16))) bf16_t sK[32 * TS];
   __shared__ __attribute__((aligned(16))) bf16_t sV[32 * TS];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l31 = lane & 31, lh = lane >> 5;
-  const int b = blockIdx.z, h = blockIdx.y;
+  const int b = blockIdx.z, h = blockIdx.y, D = a.D;
   const int qi = blockIdx.x * 128 + 32 * w + l31;
   const bf16_t* Q = (const bf16_t*)a.q;
   const bf16_t* K = (const bf16_t*)a.k;
   const bf16_t* V = (const bf16_t*)a.v;
-  bf16x8 qf[4];
-  load_b_operand(Q + ((size_t)b * a.N + min(qi, a.N - 1)) * a.ldq + h * SD, qi < a.N, lh, qf);
+  bf16x8 qf[NS];
+  load_b_operand<NS>(Q + ((size_t)b * a.N + min(qi, a.N - 1)) * a.ldq + h * D, qi < a.N, lh, D, qf);
   const int srow = tid >> 3, sch = tid & 7;
-  uint4 rk, rv;
+  uint4 rk[S::CPT], rv[S::CPT];
   auto fetch = [&](int kb) {
-    const int key = kb * 32 + srow;
-    rk = make_uint4(0, 0, 0, 0);
-    rv = rk;
-    if (key < a.NK) {
-      const size_t row = kv_row(a, b, key);
-      rk = *reinterpret_cast<const uint4*>(K + row * a.ldk + h * SD + 8 * sch);
-      rv = *reinterpret_cast<const uint4*>(V + row * a.ldv + h * SD + 8 * sch);
-    }
+    const size_t row = kv_row(a, b, min(kb * 32 + srow, a.NK - 1));
+    fetch_rows<T>(K + row * a.ldk + h * D, D, sch, rk);
+    fetch_rows<T>(V + row * a.ldv + h * D, D, sch, rv);
   };
-  f32x16 o0 = zero_acc(), o1 = zero_acc();
+  f32x16 o[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t) o[t] = zero_acc();
   float m = -INFINITY, l = 0.f;
   const float c = a.scale * 1.4426950408889634f;
   const int nkb = (a.NK + 31) / 32;
   fetch(0);
   for (int kb = 0; kb < nkb; ++kb) {
     __syncthreads();
-    *reinterpret_cast<uint4*>(sK + srow * TS + 8 * sch) = rk;
-    *reinterpret_cast<uint4*>(sV + srow * TS + 8 * sch) = rv;
+    const bool kin = kb * 32 + srow < a.NK;
+    stage_rows<T>(sK, srow, sch, kin, D, rk);
+    stage_rows<T>(sV, srow, sch, kin, D, rv);
     __syncthreads();
-    if (kb + 1 < nkb) fetch(kb + 1);
+    fetch(min(kb + 1, nkb - 1));   // the last block fetches itself again
     f32x16 st = zero_acc();
 #pragma unroll
-    for (int s = 0; s < 4; ++s)
-      st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_operand(sK, l31, s, lh), qf[s], st, 0, 0, 0);
+    for (int s = 0; s < NS; ++s)
+      if (16 * s < D) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_operand<TS>(sK, l31, s, lh), qf[s], st, 0, 0, 0);
     float mx = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -442,10 +490,9 @@ __global__ __launch_bounds__(256) void sra_fwd_mfma_kernel(const SraArgs a) {
     m = mn;
     l *= alpha;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      o0[r] *= alpha;
-      o1[r] *= alpha;
-    }
+    for (int r = 0; r < 16; ++r)
+#pragma unroll
+      for (int t = 0; t < T; ++t) o[t][r] *= alpha;
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
       bf16x8 pf;
@@ -455,36 +502,40 @@ __global__ __launch_bounds__(256) void sra_fwd_mfma_kernel(const SraArgs a) {
         l += (float)pb;   // normalise by what is actually multiplied
         pf[e] = pb;
       }
-      o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_operand(sV, 16 * s2 + 4 * lh, 0, lane), pf, o0, 0, 0, 0);
-      o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_operand(sV, 16 * s2 + 4 * lh, 32, lane), pf, o1, 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < T; ++t)
+        o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_operand<TS>(sV, 16 * s2 + 4 * lh, 32 * t, lane), pf, o[t], 0, 0, 0);
     }
   }
   l += __shfl_xor(l, 32);
   if (qi < a.N) {
-    store_t_tiles((bf16_t*)a.out + ((size_t)b * a.N + qi) * a.ldo + h * SD, lh, o0, o1, 1.f / l);
+    store_t_tiles<T>((bf16_t*)a.out + ((size_t)b * a.N + qi) * a.ldo + h * D, lh, D, o, 1.f / l);
     if (lh == 0) a.lse[((size_t)b * a.heads + h) * a.N + qi] = m + __log2f(l);
   }
 }
 
 // dQ (and delta = rowsum(dO * O), kept for the dK/dV kernel): the forward's loop with dP^T = V dO^T,
 // dS^T = P^T (dP^T - delta) * scale and dQ^T += K^T dS^T.
+template <int T>
 __global__ __launch_bounds__(256) void sra_bwd_dq_mfma_kernel(const SraArgs a) {
+  using S = SraShape<T>;
+  constexpr int TS = S::TS, NS = S::NS;
   __shared__ __attribute__((aligned(16))) bf16_t sK[32 * TS];
   __shared__ __attribute__((aligned(16))) bf16_t sV[32 * TS];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l31 = lane & 31, lh = lane >> 5;
-  const int b = blockIdx.z, h = blockIdx.y;
+  const int b = blockIdx.z, h = blockIdx.y, D = a.D;
   const int qi = blockIdx.x * 128 + 32 * w + l31;
   const bool qv = qi < a.N;
   const size_t qrow = (size_t)b * a.N + min(qi, a.N - 1);
   const bf16_t* K = (const bf16_t*)a.k;
   const bf16_t* V = (const bf16_t*)a.v;
-  bf16x8 qf[4], gf[4], of[4];
-  load_b_operand((const bf16_t*)a.q + qrow * a.ldq + h * SD, qv, lh, qf);
-  load_b_operand((const bf16_t*)a.go + qrow * a.ldgo + h * SD, qv, lh, gf);
-  load_b_operand((const bf16_t*)a.o + qrow * a.ldo + h * SD, qv, lh, of);
+  bf16x8 qf[NS], gf[NS], of[NS];
+  load_b_operand<NS>((const bf16_t*)a.q + qrow * a.ldq + h * D, qv, lh, D, qf);
+  load_b_operand<NS>((const bf16_t*)a.go + qrow * a.ldgo + h * D, qv, lh, D, gf);
+  load_b_operand<NS>((const bf16_t*)a.o + qrow * a.ldo + h * D, qv, lh, D, of);
   float delta = 0.f;
 #pragma unroll
-  for (int s = 0; s < 4; ++s)
+  for (int s = 0; s < NS; ++s)
 #pragma unroll
     for (int e = 0; e < 8; ++e) delta = fmaf((float)gf[s][e], (float)of[s][e], delta);
   delta += __shfl_xor(delta, 32);
@@ -492,32 +543,31 @@ __global__ __launch_bounds__(256) void sra_bwd_dq_mfma_kernel(const SraArgs a) {
   const float lse = qv ? a.lse[li] : INFINITY;
   if (qv && lh == 0) a.delta[li] = delta;
   const int srow = tid >> 3, sch = tid & 7;
-  uint4 rk, rv;
+  uint4 rk[S::CPT], rv[S::CPT];
   auto fetch = [&](int kb) {
-    const int key = kb * 32 + srow;
-    rk = make_uint4(0, 0, 0, 0);
-    rv = rk;
-    if (key < a.NK) {
-      const size_t row = kv_row(a, b, key);
-      rk = *reinterpret_cast<const uint4*>(K + row * a.ldk + h * SD + 8 * sch);
-      rv = *reinterpret_cast<const uint4*>(V + row * a.ldv + h * SD + 8 * sch);
-    }
+    const size_t row = kv_row(a, b, min(kb * 32 + srow, a.NK - 1));
+    fetch_rows<T>(K + row * a.ldk + h * D, D, sch, rk);
+    fetch_rows<T>(V + row * a.ldv + h * D, D, sch, rv);
   };
-  f32x16 d0 = zero_acc(), d1 = zero_acc();
+  f32x16 dq[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t) dq[t] = zero_acc();
   const float c = a.scale * 1.4426950408889634f;
   const int nkb = (a.NK + 31) / 32;
   fetch(0);
   for (int kb = 0; kb < nkb; ++kb) {
     __syncthreads();
-    *reinterpret_cast<uint4*>(sK + srow * TS + 8 * sch) = rk;
-    *reinterpret_cast<uint4*>(sV + srow * TS + 8 * sch) = rv;
+    const bool kin = kb * 32 + srow < a.NK;
+    stage_rows<T>(sK, srow, sch, kin, D, rk);
+    stage_rows<T>(sV, srow, sch, kin, D, rv);
     __syncthreads();
-    if (kb + 1 < nkb) fetch(kb + 1);
+    fetch(min(kb + 1, nkb - 1));
     f32x16 st = zero_acc(), dp = zero_acc();
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_operand(sK, l31, s, lh), qf[s], st, 0, 0, 0);
-      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_operand(sV, l31, s, lh), gf[s], dp, 0, 0, 0);
+    for (int s = 0; s < NS; ++s) {
+      if (16 * s >= D) continue;
+      st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_operand<TS>(sK, l31, s, lh), qf[s], st, 0, 0, 0);
+      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_operand<TS>(sV, l31, s, lh), gf[s], dp, 0, 0, 0);
     }
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
@@ -529,69 +579,74 @@ __global__ __launch_bounds__(256) void sra_bwd_dq_mfma_kernel(const SraArgs a) {
         const float p = key < a.NK ? __builtin_amdgcn_exp2f(st[r] * c - lse) : 0.f;
         df[e] = (bf16_t)(p * (dp[r] - delta) * a.scale);
       }
-      d0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_operand(sK, 16 * s2 + 4 * lh, 0, lane), df, d0, 0, 0, 0);
-      d1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_operand(sK, 16 * s2 + 4 * lh, 32, lane), df, d1, 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < T; ++t)
+        dq[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_operand<TS>(sK, 16 * s2 + 4 * lh, 32 * t, lane), df, dq[t], 0, 0, 0);
     }
   }
-  if (qv) store_t_tiles((bf16_t*)a.dq + qrow * a.lddq + h * SD, lh, d0, d1, 1.f);
+  if (qv) store_t_tiles<T>((bf16_t*)a.dq + qrow * a.lddq + h * D, lh, D, dq, 1.f);
 }
 
 // dK / dV: a wave owns 32 keys (its K and V rows are the B operands for the whole loop) and walks the
 // queries of its chunk in blocks of 32 staged in LDS: S = Q K^T and dP = dO V^T with the query as the
 // accumulator row, dV^T += dO^T P, dK^T += Q^T dS.  Partials per chunk go to ws, summed by sum_parts_kernel.
+template <int T>
 __global__ __launch_bounds__(256) void sra_bwd_dkv_mfma_kernel(const SraArgs a) {
+  using S = SraShape<T>;
+  constexpr int TS = S::TS, NS = S::NS;
   __shared__ __attribute__((aligned(16))) bf16_t sQ[32 * TS];
   __shared__ __attribute__((aligned(16))) bf16_t sG[32 * TS];
   __shared__ float sL[32], sD[32];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l31 = lane & 31, lh = lane >> 5;
   const int kgroups = (a.NK + 127) / 128;
-  const int b = blockIdx.z, h = blockIdx.y / kgroups, kg = blockIdx.y % kgroups;
+  const int b = blockIdx.z, h = blockIdx.y / kgroups, kg = blockIdx.y % kgroups, D = a.D;
   const int kj = kg * 128 + 32 * w + l31;
   const bool kvalid = kj < a.NK;
   const size_t krow = kv_row(a, b, min(kj, a.NK - 1));
-  bf16x8 kf[4], vf[4];
-  load_b_operand((const bf16_t*)a.k + krow * a.ldk + h * SD, kvalid, lh, kf);
-  load_b_operand((const bf16_t*)a.v + krow * a.ldv + h * SD, kvalid, lh, vf);
+  bf16x8 kf[NS], vf[NS];
+  load_b_operand<NS>((const bf16_t*)a.k + krow * a.ldk + h * D, kvalid, lh, D, kf);
+  load_b_operand<NS>((const bf16_t*)a.v + krow * a.ldv + h * D, kvalid, lh, D, vf);
   const bf16_t* Q = (const bf16_t*)a.q;
   const bf16_t* G = (const bf16_t*)a.go;
   const int q_begin = blockIdx.x * a.qc, q_end = min(a.N, q_begin + a.qc);
   const int srow = tid >> 3, sch = tid & 7;
-  uint4 rq, rg;
-  float rl = 0.f, rd = 0.f;
+  uint4 rq[S::CPT], rg[S::CPT];
+  float rl, rd;
   auto fetch = [&](int q0) {
-    const int qi = q0 + srow;
-    rq = make_uint4(0, 0, 0, 0);
-    rg = rq;
-    if (qi < q_end) {
-      const size_t row = (size_t)b * a.N + qi;
-      rq = *reinterpret_cast<const uint4*>(Q + row * a.ldq + h * SD + 8 * sch);
-      rg = *reinterpret_cast<const uint4*>(G + row * a.ldgo + h * SD + 8 * sch);
-    }
-    if (tid < 32) {
-      const int qj = q0 + tid;
-      const size_t li = ((size_t)b * a.heads + h) * a.N + min(qj, a.N - 1);
-      rl = qj < q_end ? a.lse[li] : INFINITY;   // padded query: p = exp2(-inf) = 0
-      rd = qj < q_end ? a.delta[li] : 0.f;
-    }
+    const size_t row = (size_t)b * a.N + min(q0 + srow, q_end - 1);
+    fetch_rows<T>(Q + row * a.ldq + h * D, D, sch, rq);
+    fetch_rows<T>(G + row * a.ldgo + h * D, D, sch, rg);
+    const size_t li = ((size_t)b * a.heads + h) * a.N + min(q0 + (tid & 31), q_end - 1);
+    rl = a.lse[li];
+    rd = a.delta[li];
   };
-  f32x16 dk0 = zero_acc(), dk1 = zero_acc(), dv0 = zero_acc(), dv1 = zero_acc();
+  f32x16 dk[T], dv[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+    dk[t] = zero_acc();
+    dv[t] = zero_acc();
+  }
   const float c = a.scale * 1.4426950408889634f;
-  if (q_begin < q_end) fetch(q_begin);
+  const int q_last = q_begin + ((q_end - q_begin - 1) / 32) * 32;
+  fetch(q_begin);
   for (int q0 = q_begin; q0 < q_end; q0 += 32) {
     __syncthreads();
-    *reinterpret_cast<uint4*>(sQ + srow * TS + 8 * sch) = rq;
-    *reinterpret_cast<uint4*>(sG + srow * TS + 8 * sch) = rg;
+    const bool qin = q0 + srow < q_end;
+    stage_rows<T>(sQ, srow, sch, qin, D, rq);
+    stage_rows<T>(sG, srow, sch, qin, D, rg);
     if (tid < 32) {
-      sL[tid] = rl;
-      sD[tid] = rd;
+      const bool in = q0 + tid < q_end;
+      sL[tid] = in ? rl : INFINITY;   // padded query: p = exp2(-inf) = 0
+      sD[tid] = in ? rd : 0.f;
     }
     __syncthreads();
-    if (q0 + 32 < q_end) fetch(q0 + 32);
+    fetch(min(q0 + 32, q_last));
     f32x16 st = zero_acc(), dp = zero_acc();
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_operand(sQ, l31, s, lh), kf[s], st, 0, 0, 0);
-      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_operand(sG, l31, s, lh), vf[s], dp, 0, 0, 0);
+    for (int s = 0; s < NS; ++s) {
+      if (16 * s >= D) continue;
+      st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_operand<TS>(sQ, l31, s, lh), kf[s], st, 0, 0, 0);
+      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_operand<TS>(sG, l31, s, lh), vf[s], dp, 0, 0, 0);
     }
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
@@ -604,25 +659,28 @@ __global__ __launch_bounds__(256) void sra_bwd_dkv_mfma_kernel(const SraArgs a) 
         pf[e] = (bf16_t)p;
         df[e] = (bf16_t)(p * (dp[r] - sD[qq]) * a.scale);
       }
-      dv0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_operand(sG, 16 * s2 + 4 * lh, 0, lane), pf, dv0, 0, 0, 0);
-      dv1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_operand(sG, 16 * s2 + 4 * lh, 32, lane), pf, dv1, 0, 0, 0);
-      dk0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_operand(sQ, 16 * s2 + 4 * lh, 0, lane), df, dk0, 0, 0, 0);
-      dk1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_operand(sQ, 16 * s2 + 4 * lh, 32, lane), df, dk1, 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < T; ++t)
+        dv[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_operand<TS>(sG, 16 * s2 + 4 * lh, 32 * t, lane), pf, dv[t], 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < T; ++t)
+        dk[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_operand<TS>(sQ, 16 * s2 + 4 * lh, 32 * t, lane), df, dk[t], 0, 0, 0);
     }
   }
   if (kvalid) {
-    // ws row = the kv row, columns [0, C) dK and [C, 2C) dV with C = heads * 64
-    float* o = a.ws + (size_t)blockIdx.x * a.ws_chunk + krow * a.ldws + h * SD + 4 * lh;
-    const int C = a.heads * SD;
+    // ws row = the kv row, columns [0, C) dK and [C, 2C) dV with C = heads * D
+    float* o = a.ws + (size_t)blockIdx.x * a.ws_chunk + krow * a.ldws + h * D + 4 * lh;
+    const int C = a.heads * D;
 #pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
+    for (int dt = 0; dt < T; ++dt)
 #pragma unroll
       for (int q4 = 0; q4 < 4; ++q4) {
+        if (32 * dt + 8 * q4 + 4 * lh >= D) continue;
         f32x4 k4, v4;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          k4[e] = (dt ? dk1 : dk0)[4 * q4 + e];
-          v4[e] = (dt ? dv1 : dv0)[4 * q4 + e];
+          k4[e] = dk[dt][4 * q4 + e];
+          v4[e] = dv[dt][4 * q4 + e];
         }
         *reinterpret_cast<f32x4*>(o + 32 * dt + 8 * q4) = k4;
         *reinterpret_cast<f32x4*>(o + C + 32 * dt + 8 * q4) = v4;
@@ -630,143 +688,179 @@ __global__ __launch_bounds__(256) void sra_bwd_dkv_mfma_kernel(const SraArgs a) 
   }
 }
 
-// ---- fp32 run mode: scalar kernels, one thread per query (forward, dQ) or per key (dK/dV) -----------------
+// ---- fp32 run mode: scalar kernels, one query (forward, dQ) or one key (dK/dV) per TPQ threads -------------------
+// A thread holds DH = 32T / TPQ of the padded head dims; for T > 2 two neighbouring lanes share a token and add their
+// partial dot products with one shuffle (T <= 2: one thread per token, the head dims in order, as before).
 constexpr int SF_KB = 32;   // keys (or queries) staged per block
+template <int T> struct SraF32 {
+  static constexpr int DP = 32 * T;
+  static constexpr int TPQ = T > 2 ? 2 : 1;
+  static constexpr int DH = DP / TPQ;
+};
+template <int TPQ> __device__ __forceinline__ float pair_sum(float x) {
+  if constexpr (TPQ == 2) return x + __shfl_xor(x, 1);
+  return x;
+}
 
-__global__ __launch_bounds__(128) void sra_fwd_f32_kernel(const SraArgs a) {
-  __shared__ float sK[SF_KB][SD], sV[SF_KB][SD];
-  const int b = blockIdx.z, h = blockIdx.y, qi = blockIdx.x * 128 + threadIdx.x;
-  const bool qv = qi < a.N;
-  const float* qp = (const float*)a.q + ((size_t)b * a.N + min(qi, a.N - 1)) * a.ldq + h * SD;
-  float q[SD], o[SD];
-#pragma unroll
-  for (int d = 0; d < SD; ++d) {
-    q[d] = qp[d] * a.scale;
-    o[d] = 0.f;
+// rows [r0, r0 + SF_KB) of a [row][DP] fp32 LDS tile from two token tensors, 16 bytes per load; rows >= nrows and
+// columns >= D are zero
+template <int DP, int NT, typename RowFn>
+__device__ __forceinline__ void stage_f32(float (*s0)[DP], float (*s1)[DP], const float* p0, int ld0, const float* p1,
+                                          int ld1, int nrows, int D, RowFn rowof) {
+  for (int i = threadIdx.x; i < SF_KB * DP / 4; i += NT) {
+    const int j = i / (DP / 4), d = 4 * (i % (DP / 4));
+    const size_t row = rowof(min(j, nrows - 1));
+    const f32x4 v0 = *reinterpret_cast<const f32x4*>(p0 + row * ld0 + min(d, D - 4));
+    const f32x4 v1 = *reinterpret_cast<const f32x4*>(p1 + row * ld1 + min(d, D - 4));
+    const bool ok = j < nrows && d < D;
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    *reinterpret_cast<f32x4*>(&s0[j][d]) = ok ? v0 : z;
+    *reinterpret_cast<f32x4*>(&s1[j][d]) = ok ? v1 : z;
   }
+}
+
+// this thread's DH head dims [d0, d0 + DH) of a token row, zero from column D on (clamped 16-byte loads + select)
+template <int DH>
+__device__ __forceinline__ void load_row_f32(const float* rowp, int d0, int D, float mul, float* r) {
+#pragma unroll
+  for (int c = 0; c < DH; c += 4) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(rowp + min(d0 + c, D - 4));
+    const bool in = d0 + c < D;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[c + e] = in ? v[e] * mul : 0.f;
+  }
+}
+
+template <int T>
+__global__ __launch_bounds__(128) void sra_fwd_f32_kernel(const SraArgs a) {
+  using F = SraF32<T>;
+  constexpr int DP = F::DP, TPQ = F::TPQ, DH = F::DH;
+  __shared__ float sK[SF_KB][DP], sV[SF_KB][DP];
+  const int b = blockIdx.z, h = blockIdx.y, D = a.D;
+  const int qi = blockIdx.x * (128 / TPQ) + threadIdx.x / TPQ, d0 = (threadIdx.x % TPQ) * DH;
+  const bool qv = qi < a.N;
+  const float* qp = (const float*)a.q + ((size_t)b * a.N + min(qi, a.N - 1)) * a.ldq + h * D;
+  float q[DH], o[DH];
+  load_row_f32<DH>(qp, d0, D, a.scale, q);
+#pragma unroll
+  for (int d = 0; d < DH; ++d) o[d] = 0.f;
   float m = -INFINITY, l = 0.f;
   for (int k0 = 0; k0 < a.NK; k0 += SF_KB) {
     __syncthreads();
-    for (int i = threadIdx.x; i < SF_KB * SD; i += 128) {
-      const int j = i / SD, d = i % SD;
-      float kv = 0.f, vv = 0.f;
-      if (k0 + j < a.NK) {
-        const size_t row = kv_row(a, b, k0 + j);
-        kv = ((const float*)a.k)[row * a.ldk + h * SD + d];
-        vv = ((const float*)a.v)[row * a.ldv + h * SD + d];
-      }
-      sK[j][d] = kv;
-      sV[j][d] = vv;
-    }
+    stage_f32<DP, 128>(sK, sV, (const float*)a.k + h * D, a.ldk, (const float*)a.v + h * D, a.ldv, a.NK - k0, D,
+                       [&](int j) { return kv_row(a, b, k0 + j); });
     __syncthreads();
     const int nk = min(SF_KB, a.NK - k0);
     for (int j = 0; j < nk; ++j) {
       float s = 0.f;
 #pragma unroll
-      for (int d = 0; d < SD; ++d) s = fmaf(q[d], sK[j][d], s);
+      for (int d = 0; d < DH; ++d) s = fmaf(q[d], sK[j][d0 + d], s);
+      s = pair_sum<TPQ>(s);
       const float mn = fmaxf(m, s);
       const float alpha = __expf(m - mn), p = __expf(s - mn);
       m = mn;
       l = l * alpha + p;
 #pragma unroll
-      for (int d = 0; d < SD; ++d) o[d] = fmaf(o[d], alpha, p * sV[j][d]);
+      for (int d = 0; d < DH; ++d) o[d] = fmaf(o[d], alpha, p * sV[j][d0 + d]);
     }
   }
   if (qv) {
-    float* op = (float*)a.out + ((size_t)b * a.N + qi) * a.ldo + h * SD;
+    float* op = (float*)a.out + ((size_t)b * a.N + qi) * a.ldo + h * D;
     const float inv = 1.f / l;
 #pragma unroll
-    for (int d = 0; d < SD; ++d) op[d] = o[d] * inv;
-    a.lse[((size_t)b * a.heads + h) * a.N + qi] = (m + __logf(l)) * 1.4426950408889634f;
+    for (int d = 0; d < DH; ++d)
+      if (d0 + d < D) op[d0 + d] = o[d] * inv;
+    if (d0 == 0) a.lse[((size_t)b * a.heads + h) * a.N + qi] = (m + __logf(l)) * 1.4426950408889634f;
   }
 }
 
+template <int T>
 __global__ __launch_bounds__(128) void sra_bwd_dq_f32_kernel(const SraArgs a) {
-  __shared__ float sK[SF_KB][SD], sV[SF_KB][SD];
-  const int b = blockIdx.z, h = blockIdx.y, qi = blockIdx.x * 128 + threadIdx.x;
+  using F = SraF32<T>;
+  constexpr int DP = F::DP, TPQ = F::TPQ, DH = F::DH;
+  __shared__ float sK[SF_KB][DP], sV[SF_KB][DP];
+  const int b = blockIdx.z, h = blockIdx.y, D = a.D;
+  const int qi = blockIdx.x * (128 / TPQ) + threadIdx.x / TPQ, d0 = (threadIdx.x % TPQ) * DH;
   const bool qv = qi < a.N;
   const size_t qrow = (size_t)b * a.N + min(qi, a.N - 1);
-  const float* qp = (const float*)a.q + qrow * a.ldq + h * SD;
-  const float* gp = (const float*)a.go + qrow * a.ldgo + h * SD;
-  const float* op = (const float*)a.o + qrow * a.ldo + h * SD;
-  float q[SD], g[SD], dq[SD];
+  const float* qp = (const float*)a.q + qrow * a.ldq + h * D;
+  const float* gp = (const float*)a.go + qrow * a.ldgo + h * D;
+  const float* op = (const float*)a.o + qrow * a.ldo + h * D;
+  float q[DH], g[DH], dq[DH];
+  load_row_f32<DH>(qp, d0, D, 1.f, q);
+  load_row_f32<DH>(gp, d0, D, 1.f, g);
   float delta = 0.f;
 #pragma unroll
-  for (int d = 0; d < SD; ++d) {
-    q[d] = qp[d];
-    g[d] = gp[d];
-    dq[d] = 0.f;
-    delta = fmaf(g[d], op[d], delta);
+  for (int c = 0; c < DH; c += 4) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(op + min(d0 + c, D - 4));
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      dq[c + e] = 0.f;
+      delta = fmaf(g[c + e], d0 + c < D ? v[e] : 0.f, delta);
+    }
   }
+  delta = pair_sum<TPQ>(delta);
   const size_t li = ((size_t)b * a.heads + h) * a.N + min(qi, a.N - 1);
   const float lse = a.lse[li] * 0.6931471805599453f;
-  if (qv) a.delta[li] = delta;
+  if (qv && d0 == 0) a.delta[li] = delta;
   for (int k0 = 0; k0 < a.NK; k0 += SF_KB) {
     __syncthreads();
-    for (int i = threadIdx.x; i < SF_KB * SD; i += 128) {
-      const int j = i / SD, d = i % SD;
-      float kv = 0.f, vv = 0.f;
-      if (k0 + j < a.NK) {
-        const size_t row = kv_row(a, b, k0 + j);
-        kv = ((const float*)a.k)[row * a.ldk + h * SD + d];
-        vv = ((const float*)a.v)[row * a.ldv + h * SD + d];
-      }
-      sK[j][d] = kv;
-      sV[j][d] = vv;
-    }
+    stage_f32<DP, 128>(sK, sV, (const float*)a.k + h * D, a.ldk, (const float*)a.v + h * D, a.ldv, a.NK - k0, D,
+                       [&](int j) { return kv_row(a, b, k0 + j); });
     __syncthreads();
     const int nk = min(SF_KB, a.NK - k0);
     for (int j = 0; j < nk; ++j) {
       float s = 0.f, dp = 0.f;
 #pragma unroll
-      for (int d = 0; d < SD; ++d) {
-        s = fmaf(q[d], sK[j][d], s);
-        dp = fmaf(g[d], sV[j][d], dp);
+      for (int d = 0; d < DH; ++d) {
+        s = fmaf(q[d], sK[j][d0 + d], s);
+        dp = fmaf(g[d], sV[j][d0 + d], dp);
       }
+      s = pair_sum<TPQ>(s);
+      dp = pair_sum<TPQ>(dp);
       const float ds = __expf(s * a.scale - lse) * (dp - delta) * a.scale;
 #pragma unroll
-      for (int d = 0; d < SD; ++d) dq[d] = fmaf(ds, sK[j][d], dq[d]);
+      for (int d = 0; d < DH; ++d) dq[d] = fmaf(ds, sK[j][d0 + d], dq[d]);
     }
   }
   if (qv) {
-    float* dp_ = (float*)a.dq + qrow * a.lddq + h * SD;
+    float* dp_ = (float*)a.dq + qrow * a.lddq + h * D;
 #pragma unroll
-    for (int d = 0; d < SD; ++d) dp_[d] = dq[d];
+    for (int d = 0; d < DH; ++d)
+      if (d0 + d < D) dp_[d0 + d] = dq[d];
   }
 }
 
-// one thread per key; blockIdx.x = query chunk; PASS 0: dV, PASS 1: dK (each keeps k and one accumulator row)
-template <int PASS>
+// keys per workgroup of the fp32 dK/dV kernel (64 threads)
+inline int sra_f32_kpb(int D) { return D > 64 ? 32 : 64; }
+
+// one key per TPQ threads; blockIdx.x = query chunk; PASS 0: dV, PASS 1: dK (each keeps k and one accumulator row)
+template <int T, int PASS>
 __global__ __launch_bounds__(64) void sra_bwd_dkv_f32_kernel(const SraArgs a) {
-  __shared__ float sQ[SF_KB][SD], sG[SF_KB][SD], sL[SF_KB], sD[SF_KB];
-  const int kgroups = (a.NK + 63) / 64;
-  const int b = blockIdx.z, h = blockIdx.y / kgroups, kj = (blockIdx.y % kgroups) * 64 + threadIdx.x;
+  using F = SraF32<T>;
+  constexpr int DP = F::DP, TPQ = F::TPQ, DH = F::DH, KPB = 64 / TPQ;
+  __shared__ float sQ[SF_KB][DP], sG[SF_KB][DP], sL[SF_KB], sD[SF_KB];
+  const int kgroups = (a.NK + KPB - 1) / KPB, D = a.D;
+  const int b = blockIdx.z, h = blockIdx.y / kgroups, kj = (blockIdx.y % kgroups) * KPB + threadIdx.x / TPQ;
+  const int d0 = (threadIdx.x % TPQ) * DH;
   const bool kvalid = kj < a.NK;
   const size_t krow = kv_row(a, b, min(kj, a.NK - 1));
-  const float* kp = (const float*)a.k + krow * a.ldk + h * SD;
-  const float* vp = (const float*)a.v + krow * a.ldv + h * SD;
-  float k[SD], v[SD], acc[SD];
+  const float* kp = (const float*)a.k + krow * a.ldk + h * D;
+  const float* vp = (const float*)a.v + krow * a.ldv + h * D;
+  float k[DH], v[DH], acc[DH];
+  load_row_f32<DH>(kp, d0, D, 1.f, k);
+  if (PASS) load_row_f32<DH>(vp, d0, D, 1.f, v);
 #pragma unroll
-  for (int d = 0; d < SD; ++d) {
-    k[d] = kp[d];
-    v[d] = PASS ? vp[d] : 0.f;
+  for (int d = 0; d < DH; ++d) {
+    if (!PASS) v[d] = 0.f;
     acc[d] = 0.f;
   }
   const int q_begin = blockIdx.x * a.qc, q_end = min(a.N, q_begin + a.qc);
   for (int q0 = q_begin; q0 < q_end; q0 += SF_KB) {
     __syncthreads();
     const int nq = min(SF_KB, q_end - q0);
-    for (int i = threadIdx.x; i < SF_KB * SD; i += 64) {
-      const int j = i / SD, d = i % SD;
-      float qv = 0.f, gv = 0.f;
-      if (j < nq) {
-        const size_t row = (size_t)b * a.N + q0 + j;
-        qv = ((const float*)a.q)[row * a.ldq + h * SD + d];
-        gv = ((const float*)a.go)[row * a.ldgo + h * SD + d];
-      }
-      sQ[j][d] = qv;
-      sG[j][d] = gv;
-    }
+    stage_f32<DP, 64>(sQ, sG, (const float*)a.q + h * D, a.ldq, (const float*)a.go + h * D, a.ldgo, nq, D,
+                      [&](int j) { return (size_t)b * a.N + q0 + j; });
     if (threadIdx.x < SF_KB && threadIdx.x < nq) {
       const size_t li = ((size_t)b * a.heads + h) * a.N + q0 + threadIdx.x;
       sL[threadIdx.x] = a.lse[li] * 0.6931471805599453f;
@@ -776,25 +870,28 @@ __global__ __launch_bounds__(64) void sra_bwd_dkv_f32_kernel(const SraArgs a) {
     for (int j = 0; j < nq; ++j) {
       float s = 0.f, dp = 0.f;
 #pragma unroll
-      for (int d = 0; d < SD; ++d) {
-        s = fmaf(sQ[j][d], k[d], s);
-        if (PASS) dp = fmaf(sG[j][d], v[d], dp);
+      for (int d = 0; d < DH; ++d) {
+        s = fmaf(sQ[j][d0 + d], k[d], s);
+        if (PASS) dp = fmaf(sG[j][d0 + d], v[d], dp);
       }
+      s = pair_sum<TPQ>(s);
+      if (PASS) dp = pair_sum<TPQ>(dp);
       const float p = __expf(s * a.scale - sL[j]);
       if (PASS) {
         const float ds = p * (dp - sD[j]) * a.scale;
 #pragma unroll
-        for (int d = 0; d < SD; ++d) acc[d] = fmaf(ds, sQ[j][d], acc[d]);
+        for (int d = 0; d < DH; ++d) acc[d] = fmaf(ds, sQ[j][d0 + d], acc[d]);
       } else {
 #pragma unroll
-        for (int d = 0; d < SD; ++d) acc[d] = fmaf(p, sG[j][d], acc[d]);
+        for (int d = 0; d < DH; ++d) acc[d] = fmaf(p, sG[j][d0 + d], acc[d]);
       }
     }
   }
   if (kvalid) {
-    float* o = a.ws + (size_t)blockIdx.x * a.ws_chunk + krow * a.ldws + h * SD + (PASS ? 0 : a.heads * SD);
+    float* o = a.ws + (size_t)blockIdx.x * a.ws_chunk + krow * a.ldws + h * D + (PASS ? 0 : a.heads * D);
 #pragma unroll
-    for (int d = 0; d < SD; ++d) o[d] = acc[d];
+    for (int d = 0; d < DH; ++d)
+      if (d0 + d < D) o[d0 + d] = acc[d];
   }
 }
 
@@ -802,11 +899,13 @@ int sra_check(const char* fn, const uz_sra_desc* d) {
   UZ_REQUIRE(d != nullptr, "%s: null descriptor", fn);
   UZ_REQUIRE(d->dtype == UZ_F32 || d->dtype == UZ_BF16, "%s: bad dtype", fn);
   const int vec = d->dtype == UZ_BF16 ? 8 : 4;
-  UZ_REQUIRE(d->B > 0 && d->N > 0 && d->NK > 0 && d->heads > 0 && d->B <= 65535 && d->heads * ((d->NK + 63) / 64) <= 65535,
+  UZ_REQUIRE(d->head_dim >= SD_MIN && d->head_dim <= SD_MAX && d->head_dim % 8 == 0,
+             "%s: head_dim %d unsupported (the kernels take multiples of 8 from %d to %d)", fn, d->head_dim, SD_MIN, SD_MAX);
+  const int kpb = sra_f32_kpb(d->head_dim);
+  UZ_REQUIRE(d->B > 0 && d->N > 0 && d->NK > 0 && d->heads > 0 && d->B <= 65535 && d->heads * ((d->NK + kpb - 1) / kpb) <= 65535,
              "%s: bad shape B=%d N=%d NK=%d heads=%d", fn, d->B, d->N, d->NK, d->heads);
-  UZ_REQUIRE(d->head_dim == SD, "%s: head_dim %d unsupported (the kernels are built for 64)", fn, d->head_dim);
   UZ_REQUIRE(d->kps > 0 && d->NK % d->kps == 0, "%s: NK=%d is not a multiple of the segment length %d", fn, d->NK, d->kps);
-  const int C = d->heads * SD;
+  const int C = d->heads * d->head_dim;
   UZ_REQUIRE(d->ldq >= C && d->ldk >= C && d->ldv >= C && d->ldo >= C && d->ldq % vec == 0 && d->ldk % vec == 0 &&
                  d->ldv % vec == 0 && d->ldo % vec == 0, "%s: bad leading dimensions", fn);
   UZ_REQUIRE((long long)d->B * d->N < (1LL << 31) && (long long)d->B * d->NK < (1LL << 31), "%s: too many rows", fn);
@@ -814,14 +913,14 @@ int sra_check(const char* fn, const uz_sra_desc* d) {
 }
 
 void sra_fill(const uz_sra_desc* d, SraArgs* a) {
-  a->B = d->B; a->N = d->N; a->NK = d->NK; a->heads = d->heads; a->kps = d->kps;
+  a->B = d->B; a->N = d->N; a->NK = d->NK; a->heads = d->heads; a->kps = d->kps; a->D = d->head_dim;
   a->ldq = d->ldq; a->ldk = d->ldk; a->ldv = d->ldv; a->ldo = d->ldo;
   a->scale = d->scale;
 }
 
 // query chunks of the dK/dV kernel: enough workgroups to fill the chip, chunks of at least 64 queries
 void sra_chunks(const uz_sra_desc* d, int* qc, int* nchunks) {
-  const int per = d->dtype == UZ_BF16 ? 128 : 64;
+  const int per = d->dtype == UZ_BF16 ? 128 : sra_f32_kpb(d->head_dim);
   const long long base = (long long)d->B * d->heads * ((d->NK + per - 1) / per);
   const int nqb = (d->N + 31) / 32;
   long long want = (4LL * UZ_NUM_CU + base - 1) / base;
@@ -835,6 +934,36 @@ void sra_chunks(const uz_sra_desc* d, int* qc, int* nchunks) {
 
 // floats of the delta vector, rounded so the partial tiles that follow stay 64-byte aligned
 long long sra_delta_floats(const uz_sra_desc* d) { return (((long long)d->B * d->heads * d->N + 15) / 16) * 16; }
+
+template <int T> void sra_launch_fwd(const uz_sra_desc* d, const SraArgs& a, hipStream_t s) {
+  if (d->dtype == UZ_BF16) {
+    hipLaunchKernelGGL(sra_fwd_mfma_kernel<T>, dim3((d->N + 127) / 128, d->heads, d->B), dim3(256), 0, s, a);
+  } else {
+    constexpr int qpb = 128 / SraF32<T>::TPQ;
+    hipLaunchKernelGGL(sra_fwd_f32_kernel<T>, dim3((d->N + qpb - 1) / qpb, d->heads, d->B), dim3(128), 0, s, a);
+  }
+}
+
+template <int T> int sra_launch_bwd(const uz_sra_desc* d, const SraArgs& a, int nchunks, void* dkv, hipStream_t s) {
+  if (d->dtype == UZ_BF16) {
+    hipLaunchKernelGGL(sra_bwd_dq_mfma_kernel<T>, dim3((d->N + 127) / 128, d->heads, d->B), dim3(256), 0, s, a);
+    UZ_LAUNCH_CHECK("uz_sra_bwd(dq)");
+    hipLaunchKernelGGL(sra_bwd_dkv_mfma_kernel<T>, dim3(nchunks, d->heads * ((d->NK + 127) / 128), d->B), dim3(256), 0, s, a);
+    UZ_LAUNCH_CHECK("uz_sra_bwd(dkv)");
+    hipLaunchKernelGGL((sum_parts_kernel<bf16_t>), dim3(grid_cap(a.ws_chunk / 4, 256)), dim3(256), 0, s, a.ws, nchunks, a.ws_chunk, (bf16_t*)dkv);
+  } else {
+    constexpr int qpb = 128 / SraF32<T>::TPQ, kpb = 64 / SraF32<T>::TPQ;
+    hipLaunchKernelGGL(sra_bwd_dq_f32_kernel<T>, dim3((d->N + qpb - 1) / qpb, d->heads, d->B), dim3(128), 0, s, a);
+    UZ_LAUNCH_CHECK("uz_sra_bwd(dq)");
+    const dim3 gk(nchunks, d->heads * ((d->NK + kpb - 1) / kpb), d->B);
+    hipLaunchKernelGGL((sra_bwd_dkv_f32_kernel<T, 0>), gk, dim3(64), 0, s, a);
+    hipLaunchKernelGGL((sra_bwd_dkv_f32_kernel<T, 1>), gk, dim3(64), 0, s, a);
+    UZ_LAUNCH_CHECK("uz_sra_bwd(dkv)");
+    hipLaunchKernelGGL((sum_parts_kernel<float>), dim3(grid_cap(a.ws_chunk / 4, 256)), dim3(256), 0, s, a.ws, nchunks, a.ws_chunk, (float*)dkv);
+  }
+  UZ_LAUNCH_CHECK("uz_sra_bwd(sum)");
+  return UZ_OK;
+}
 
 }  // namespace
 
@@ -915,20 +1044,26 @@ extern "C" int uz_dwconv3x3_wgrad(int dtype, const void* x, int ldx, const void*
   return UZ_OK;
 }
 
-extern "C" int uz_space_to_depth(int dtype, const void* src, int lds_, void* dst, int ldd, int N, int Ho, int Wo, int C,
-                                 int r, int inverse, void* stream) {
+extern "C" int uz_space_to_depth_crop(int dtype, const void* src, int lds_, void* dst, int ldd, int N, int H, int W,
+                                      int C, int r, int inverse, void* stream) {
   UZ_REQUIRE(dtype == UZ_F32 || dtype == UZ_BF16, "uz_space_to_depth: bad dtype");
   const int vec = dtype == UZ_BF16 ? 8 : 4;
-  UZ_REQUIRE(src && dst && N > 0 && Ho > 0 && Wo > 0 && C > 0 && r > 0 && C % vec == 0, "uz_space_to_depth: bad shape");
+  UZ_REQUIRE(src && dst && N > 0 && r > 0 && H >= r && W >= r && C > 0 && C % vec == 0, "uz_space_to_depth: bad shape");
   const int lfine = inverse ? ldd : lds_, lcoarse = inverse ? lds_ : ldd;
   UZ_REQUIRE(lfine % vec == 0 && lcoarse % vec == 0 && lfine >= C && lcoarse >= r * r * C, "uz_space_to_depth: bad strides");
-  const long long total = (long long)N * Ho * r * Wo * r * (C / vec);
+  const long long total = (long long)N * H * W * (C / vec);
   const dim3 grid(grid_cap(total, 256)), block(256);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == UZ_BF16) hipLaunchKernelGGL((space_to_depth_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)src, lds_, (bf16_t*)dst, ldd, N, Ho, Wo, C, r, inverse);
-  else hipLaunchKernelGGL((space_to_depth_kernel<float>), grid, block, 0, s, (const float*)src, lds_, (float*)dst, ldd, N, Ho, Wo, C, r, inverse);
+  if (dtype == UZ_BF16) hipLaunchKernelGGL((space_to_depth_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)src, lds_, (bf16_t*)dst, ldd, N, H, W, C, r, inverse);
+  else hipLaunchKernelGGL((space_to_depth_kernel<float>), grid, block, 0, s, (const float*)src, lds_, (float*)dst, ldd, N, H, W, C, r, inverse);
   UZ_LAUNCH_CHECK("uz_space_to_depth");
   return UZ_OK;
+}
+
+extern "C" int uz_space_to_depth(int dtype, const void* src, int lds_, void* dst, int ldd, int N, int Ho, int Wo, int C,
+                                 int r, int inverse, void* stream) {
+  UZ_REQUIRE(Ho > 0 && Wo > 0 && r > 0, "uz_space_to_depth: bad shape");
+  return uz_space_to_depth_crop(dtype, src, lds_, dst, ldd, N, Ho * r, Wo * r, C, r, inverse, stream);
 }
 
 extern "C" int uz_im2col_nchw(int dtype, const float* x_nchw, int N, int C, int H, int W, int k, int stride, int pad,
@@ -954,10 +1089,13 @@ extern "C" int uz_sra_fwd(const uz_sra_desc* d, const void* q, const void* k, co
   SraArgs a{};
   sra_fill(d, &a);
   a.q = q; a.k = k; a.v = v; a.out = out; a.lse = lse;
-  const dim3 grid((d->N + 127) / 128, d->heads, d->B);
   hipStream_t s = (hipStream_t)stream;
-  if (d->dtype == UZ_BF16) hipLaunchKernelGGL(sra_fwd_mfma_kernel, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(sra_fwd_f32_kernel, grid, dim3(128), 0, s, a);
+  switch ((d->head_dim + 31) / 32) {
+    case 1: sra_launch_fwd<1>(d, a, s); break;
+    case 2: sra_launch_fwd<2>(d, a, s); break;
+    case 3: sra_launch_fwd<3>(d, a, s); break;
+    default: sra_launch_fwd<4>(d, a, s); break;
+  }
   UZ_LAUNCH_CHECK("uz_sra_fwd");
   return UZ_OK;
 }
@@ -967,7 +1105,7 @@ extern "C" long long uz_sra_bwd_workspace_bytes(const uz_sra_desc* d) {
   int qc, nchunks;
   sra_chunks(d, &qc, &nchunks);
   // delta [B][heads][N] + partial dK/dV [chunks][kv rows][2C]
-  return (sra_delta_floats(d) + (long long)nchunks * d->B * d->NK * 2 * d->heads * SD) * 4;
+  return (sra_delta_floats(d) + (long long)nchunks * d->B * d->NK * 2 * d->heads * d->head_dim) * 4;
 }
 
 extern "C" int uz_sra_bwd(const uz_sra_desc* d, const void* q, const void* k, const void* v, const void* o,
@@ -975,10 +1113,10 @@ extern "C" int uz_sra_bwd(const uz_sra_desc* d, const void* q, const void* k, co
                           void* workspace, void* stream) {
   const int rc = sra_check("uz_sra_bwd", d);
   if (rc != UZ_OK) return rc;
-  const int vec = d->dtype == UZ_BF16 ? 8 : 4, C = d->heads * SD;
+  const int vec = d->dtype == UZ_BF16 ? 8 : 4, C = d->heads * d->head_dim;
   UZ_REQUIRE(q && k && v && o && lse && go && dq && dkv && workspace, "uz_sra_bwd: null pointer");
   UZ_REQUIRE(ldgo >= C && lddq >= C && ldgo % vec == 0 && lddq % vec == 0, "uz_sra_bwd: bad gradient strides");
-  UZ_REQUIRE(lddkv == 2 * C, "uz_sra_bwd: dkv must be a dense [B * NK][2 * heads * 64] tensor (lddkv = %d)", lddkv);
+  UZ_REQUIRE(lddkv == 2 * C, "uz_sra_bwd: dkv must be a dense [B * NK][2 * heads * head_dim] tensor (lddkv = %d)", lddkv);
   SraArgs a{};
   sra_fill(d, &a);
   a.q = q; a.k = k; a.v = v; a.o = o; a.go = go; a.dq = dq; a.lse = const_cast<float*>(lse);
@@ -989,22 +1127,10 @@ extern "C" int uz_sra_bwd(const uz_sra_desc* d, const void* q, const void* k, co
   a.ws = a.delta + sra_delta_floats(d);
   a.ws_chunk = (long long)d->B * d->NK * 2 * C;
   hipStream_t s = (hipStream_t)stream;
-  const dim3 gq((d->N + 127) / 128, d->heads, d->B);
-  if (d->dtype == UZ_BF16) {
-    hipLaunchKernelGGL(sra_bwd_dq_mfma_kernel, gq, dim3(256), 0, s, a);
-    UZ_LAUNCH_CHECK("uz_sra_bwd(dq)");
-    hipLaunchKernelGGL(sra_bwd_dkv_mfma_kernel, dim3(nchunks, d->heads * ((d->NK + 127) / 128), d->B), dim3(256), 0, s, a);
-    UZ_LAUNCH_CHECK("uz_sra_bwd(dkv)");
-    hipLaunchKernelGGL((sum_parts_kernel<bf16_t>), dim3(grid_cap(a.ws_chunk / 4, 256)), dim3(256), 0, s, a.ws, nchunks, a.ws_chunk, (bf16_t*)dkv);
-  } else {
-    hipLaunchKernelGGL(sra_bwd_dq_f32_kernel, gq, dim3(128), 0, s, a);
-    UZ_LAUNCH_CHECK("uz_sra_bwd(dq)");
-    const dim3 gk(nchunks, d->heads * ((d->NK + 63) / 64), d->B);
-    hipLaunchKernelGGL((sra_bwd_dkv_f32_kernel<0>), gk, dim3(64), 0, s, a);
-    hipLaunchKernelGGL((sra_bwd_dkv_f32_kernel<1>), gk, dim3(64), 0, s, a);
-    UZ_LAUNCH_CHECK("uz_sra_bwd(dkv)");
-    hipLaunchKernelGGL((sum_parts_kernel<float>), dim3(grid_cap(a.ws_chunk / 4, 256)), dim3(256), 0, s, a.ws, nchunks, a.ws_chunk, (float*)dkv);
+  switch ((d->head_dim + 31) / 32) {
+    case 1: return sra_launch_bwd<1>(d, a, nchunks, dkv, s);
+    case 2: return sra_launch_bwd<2>(d, a, nchunks, dkv, s);
+    case 3: return sra_launch_bwd<3>(d, a, nchunks, dkv, s);
+    default: return sra_launch_bwd<4>(d, a, nchunks, dkv, s);
   }
-  UZ_LAUNCH_CHECK("uz_sra_bwd(sum)");
-  return UZ_OK;
 }

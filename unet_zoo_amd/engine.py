@@ -651,10 +651,11 @@ class Engine:
             self.tape.append(bwd)
         return (act, pooled) if pool else act
 
-    def conv_plain(self, x: Act, conv: nn.Conv2d, *, im2col: bool = False) -> Act:
+    def conv_plain(self, x: Act, conv: nn.Conv2d, *, im2col: bool = False, residual: Optional[Act] = None) -> Act:
         """Conv2d k3 p1 / k1 p0, stride 1, WITHOUT a following BatchNorm: the block tails and skip convolutions of
         resunet (resunet.py:28-32, common_layers.py:191, :194 after uz-side subsampling).  `im2col`: x holds the
-        3x3 patches of the network input (input_im2col)."""
+        3x3 patches of the network input (input_im2col).  `residual`: y = conv(x) + residual in the GEMM's epilogue
+        (UNeXt's `decoder_level1(x) + x2`), its gradient handed back as in linear()."""
         Cout = conv.out_channels
         k = conv.kernel_size[0]
         assert conv.kernel_size in ((3, 3), (1, 1)) and conv.dilation == (1, 1)
@@ -666,12 +667,14 @@ class Engine:
             assert conv.in_channels == x.C
             wp, ntaps = self._pack(conv.weight, L.PACK_CONV_FWD), k * k
         y = self.new_act(x.N, x.H, x.W, Cout)
-        ops.conv_igemm(x, wp, conv.bias.detach() if conv.bias is not None else None, y, ntaps=ntaps)
+        ops.conv_igemm(x, wp, conv.bias.detach() if conv.bias is not None else None, y, ntaps=ntaps, res=residual)
         if self.record:
             def bwd():
                 g = self._total_grad(y)
                 if g is None:
                     return
+                if residual is not None and residual.needs_grad:
+                    residual.add_grad(g)
                 if conv.bias is not None:
                     self._bias_grad(conv.bias, g)
                 if im2col:
@@ -1066,10 +1069,11 @@ class Engine:
     def patch_conv(self, x: Act, conv: nn.Conv2d, out: Optional[Act] = None) -> Act:
         """Conv2d(C, C', r, r) with stride r (EfficientSelfAtten.sr / Scale_reduce.sr_convs, missformer.py:17,76):
         space-to-depth, then the token GEMM over r*r*C columns; its input gradient is the transposed GEMM
-        scattered back (= ConvTranspose2d with the same weight)."""
+        scattered back (= ConvTranspose2d with the same weight).  A map that r does not divide loses its bottom / right
+        border, as Conv2d's floor does (unext.py Attention.sr); that border's input gradient is zero."""
         r = conv.kernel_size[0]
         assert conv.kernel_size == conv.stride == (r, r) and conv.padding == (0, 0) and conv.in_channels == x.C
-        assert x.H % r == 0 and x.W % r == 0, f"map {x.H}x{x.W} is not a multiple of the reduction ratio {r}"
+        assert x.H >= r and x.W >= r, f"map {x.H}x{x.W} is smaller than the reduction ratio {r}"
         Cout, T = conv.out_channels, r * r
         xs = self.new_act(x.N, x.H // r, x.W // r, T * x.C)
         ops.space_to_depth(x, xs, r)
@@ -1142,7 +1146,8 @@ class Engine:
 
     def sr_attention(self, q: Act, kv: Act, B: int, heads: int, kps: int, scale: float,
                      segments: Optional[Sequence[Tuple[int, int]]] = None) -> Act:
-        """softmax(q k^T * scale) v per (image, head), head_dim 64 (missformer.py:30-36, :122-125).  `segments`:
+        """softmax(q k^T * scale) v per (image, head), head_dim q.C / heads: a multiple of 8 up to 128 (missformer.py:30-36,
+        :122-125; unext.py Attention).  `segments`:
         (first row, queries per image) of the row blocks of q that attend to the same keys (the bridge's four
         scales, each stored [B][n_s]); default: q is one [B][N] block."""
         if segments is None:
@@ -1986,6 +1991,27 @@ class Engine:
                     x.add_grad(dx)
 
             self._heads.append((bwd, 1))
+        return logits
+
+    def out_conv_resized(self, x: Act, conv: nn.Conv2d, H: int, W: int, align_corners: bool = True) -> torch.Tensor:
+        """conv(F.interpolate(x, size=(H, W), mode='bilinear', align_corners=...)) for a 1x1 `conv`, (N, K, H, W) fp32,
+        computed as the resize of conv(x): both maps are linear and the bilinear weights of an output pixel sum to 1,
+        so only the fp32 rounding differs.  No (H, W, x.C) tensor exists in the forward or the backward: the 1x1
+        convolution and its weight / bias / input gradients run at x's resolution, the resize on the K logit planes."""
+        low = self.out_conv(x, conv)
+        N, K, h, w = low.shape
+        logits = torch.empty((N, K, H, W), dtype=torch.float32, device=low.device)
+        ops.bilinear_planes_ac(low.data_ptr(), h, w, logits.data_ptr(), H, W, N * K, align_corners)
+        if self.record:
+            inner, n = self._heads.pop()
+
+            def bwd(g_logits: torch.Tensor):
+                g_low = torch.empty((N, K, h, w), dtype=torch.float32, device=low.device)
+                ops.bilinear_planes_ac(g_logits.contiguous().float().data_ptr(), h, w, g_low.data_ptr(), H, W, N * K,
+                                       align_corners, backward=True)
+                inner(g_low)
+
+            self._heads.append((bwd, n))
         return logits
 
     def layer_norm_head(self, x: Act, ln: nn.LayerNorm, conv: nn.Conv2d, *, mode: int = L.LN_PLAIN, r: int = 1) -> torch.Tensor:

@@ -24,6 +24,7 @@ from .transatt_unet import TransAttUNet
 from .unet_transformer import U_Transformer
 from .multiresunet import MultiResUnet
 from .uctransnet import UCTransNet, get_uctransnet_config
+from .unext import UNext, UNext_S
 
 # every name the reference registers (models/__init__.py:27-52); value = constructor or None
 _model_entries: Dict[str, Optional[Callable[..., nn.Module]]] = {
@@ -44,8 +45,8 @@ _model_entries: Dict[str, Optional[Callable[..., nn.Module]]] = {
     'resunet': ResUnet,
     'wranet': None,
     'egeunet': None,
-    'unext': None,
-    'unext_s': None,
+    'unext': UNext,
+    'unext_s': UNext_S,
     'mmunet': None,
     'axialunet': None,
     'gated': None,
@@ -125,6 +126,15 @@ def create_model(model_name: str, pretrained: bool = False, **kwargs) -> nn.Modu
         # models/__init__.py:139-143: depth travels to the constructor (absorbed by **kwargs there)
         args.update(in_channels=in_channels, num_classes=num_classes, depth=depth,
                     deep_supervision=kwargs.pop('deep_supervision', False))
+    elif name in ('unext', 'unext_s'):
+        # models/__init__.py:185-199: input_channels / img_size (default 224); the structure and rate arguments travel
+        # as given (UNext_S drops the five structure ones itself)
+        args.update(input_channels=in_channels, num_classes=num_classes,
+                    img_size=image_size if image_size is not None else 224)
+        for k, default in (('embed_dims', None), ('num_heads', None), ('mlp_ratios', None), ('qkv_bias', False),
+                           ('qk_scale', None), ('drop_rate', 0.0), ('attn_drop_rate', 0.0), ('drop_path_rate', 0.0),
+                           ('norm_layer', nn.LayerNorm), ('depths', None), ('sr_ratios', None)):
+            args[k] = kwargs.pop(k, default)
     else:
         args.update(in_channels=in_channels, num_classes=num_classes)
     args.update(kwargs)  # leftovers reach the constructor: unknown ones raise TypeError there
@@ -135,4 +145,4 @@ def create_model(model_name: str, pretrained: bool = False, **kwargs) -> nn.Modu
     return model
 
 
-__all__ = ['UNet', 'AttentionUNet', 'U2NET', 'U2NETP', 'SwinTransformerSys', 'NestedUNet', 'ResUnet', 'MISSFormer', 'TransAttUNet', 'U_Transformer', 'MultiResUnet', 'UCTransNet', 'list_models', 'hip_models', 'get_model_config', 'create_model']
+__all__ = ['UNet', 'AttentionUNet', 'U2NET', 'U2NETP', 'SwinTransformerSys', 'NestedUNet', 'ResUnet', 'MISSFormer', 'TransAttUNet', 'U_Transformer', 'MultiResUnet', 'UCTransNet', 'UNext', 'UNext_S', 'list_models', 'hip_models', 'get_model_config', 'create_model']

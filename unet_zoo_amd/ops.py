@@ -880,6 +880,21 @@ def bilinear_planes(src_ptr: int, src_img: int, hi: int, wi: int, dst_ptr: int, 
                 "uz_bilinear(planes)")
 
 
+def bilinear_planes_ac(src_ptr: int, hi: int, wi: int, dst_ptr: int, ho: int, wo: int, n: int, align_corners: bool,
+                       backward: bool = False) -> None:
+    """n dense fp32 single-channel planes resized (hi, wi) -> (ho, wo) with the given align_corners (the logit maps of
+    Engine.out_conv_resized).  backward: src is the gradient at (ho, wo), dst the gradient at (hi, wi)."""
+    lib = L.load()
+    fn = lib.uz_resize_bilinear_bwd if backward else lib.uz_resize_bilinear_fwd
+    with _Timed("bilinear_planes_bwd" if backward else "bilinear_planes_fwd", 0.0, 4.0 * n * (hi * wi + ho * wo)):
+        if backward:
+            L.check(fn(L.UZ_F32, src_ptr, 1, ho * wo, n, hi, wi, 1, dst_ptr, 1, hi * wi, ho, wo, int(align_corners),
+                       L.stream_ptr()), "uz_resize_bilinear_bwd(planes)")
+        else:
+            L.check(fn(L.UZ_F32, src_ptr, 1, hi * wi, n, hi, wi, 1, dst_ptr, 1, ho * wo, ho, wo, int(align_corners),
+                       L.stream_ptr()), "uz_resize_bilinear_fwd(planes)")
+
+
 def pool_grad_combine(act: Act, g0: Optional[Act], g1: Optional[Act], gp: Optional[Act], out: Act,
                       pool_ceil: bool = False) -> None:
     if g0 is None:
@@ -1183,14 +1198,21 @@ def dwconv3x3_wgrad(x: Act, g: Act, defer: Optional[list] = None) -> torch.Tenso
 
 
 def space_to_depth(src: Act, dst: Act, r: int, inverse: bool = False) -> None:
-    """dst[n, ho, wo, (ty*r+tx)*C + c] = src[n, ho*r+ty, wo*r+tx, c]; inverse: the scatter back"""
+    """dst[n, ho, wo, (ty*r+tx)*C + c] = src[n, ho*r+ty, wo*r+tx, c]; inverse: the scatter back.  The coarse map is
+    floor(H / r) x floor(W / r) of the fine one: the border a Conv2d(r, stride r) drops is not read, and its gradient
+    (inverse) is written as zeros."""
     fine, coarse = (dst, src) if inverse else (src, dst)
-    assert fine.N == coarse.N and fine.H == coarse.H * r and fine.W == coarse.W * r and coarse.C == r * r * fine.C
+    assert fine.N == coarse.N and fine.H // r == coarse.H and fine.W // r == coarse.W and coarse.C == r * r * fine.C
     assert src.dtype == dst.dtype
     with _Timed("space_to_depth", 0.0, 2 * src.buf.element_size() * fine.P * fine.C):
-        L.check(L.load().uz_space_to_depth(L.dtype_code(src.dtype), src.ptr(), src.ld, dst.ptr(), dst.ld, coarse.N,
-                                           coarse.H, coarse.W, fine.C, r, 1 if inverse else 0, L.stream_ptr()),
-                "uz_space_to_depth")
+        if fine.H == coarse.H * r and fine.W == coarse.W * r:
+            L.check(L.load().uz_space_to_depth(L.dtype_code(src.dtype), src.ptr(), src.ld, dst.ptr(), dst.ld, coarse.N,
+                                               coarse.H, coarse.W, fine.C, r, 1 if inverse else 0, L.stream_ptr()),
+                    "uz_space_to_depth")
+        else:
+            L.check(L.load().uz_space_to_depth_crop(L.dtype_code(src.dtype), src.ptr(), src.ld, dst.ptr(), dst.ld, fine.N,
+                                                    fine.H, fine.W, fine.C, r, 1 if inverse else 0, L.stream_ptr()),
+                    "uz_space_to_depth_crop")
 
 
 def im2col_nchw(x: torch.Tensor, k: int, stride: int, pad: int, kpad: int, dtype: torch.dtype) -> Act:
@@ -1205,9 +1227,9 @@ def im2col_nchw(x: torch.Tensor, k: int, stride: int, pad: int, kpad: int, dtype
 
 
 def _sra_desc(q: Act, kv: Act, B: int, heads: int, kps: int, scale: float, ldo: int) -> "L.SraDesc":
-    C = heads * 64
-    assert q.C == C and kv.C == 2 * C and q.P % B == 0 and kv.P % B == 0 and q.dtype == kv.dtype
-    return L.SraDesc(L.dtype_code(q.dtype), B, q.P // B, kv.P // B, heads, 64, kps, q.ld, kv.ld, kv.ld, ldo, scale)
+    C = q.C
+    assert C % heads == 0 and kv.C == 2 * C and q.P % B == 0 and kv.P % B == 0 and q.dtype == kv.dtype
+    return L.SraDesc(L.dtype_code(q.dtype), B, q.P // B, kv.P // B, heads, C // heads, kps, q.ld, kv.ld, kv.ld, ldo, scale)
 
 
 def sra_fwd(q: Act, kv: Act, out: Act, B: int, heads: int, kps: int, scale: float) -> torch.Tensor:
