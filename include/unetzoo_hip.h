@@ -812,6 +812,67 @@ int uz_chanattn_probs_fwd(int dtype, const float* scores, int B, int H, int C, i
 int uz_chanattn_probs_bwd(int dtype, const float* scores, const float* dpc, int B, int H, int C, int KV, float scale,
                           float eps, void* ds, void* ds_t, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * VNet (unet_zoo/models/vnet.py): k x k convolution with k = 5 (zero padding 2) or k = 1, stride 1, NHWC, and the
+ * BatchNorm + ELU element passes around it (uz_conv5x5.hip).
+ *
+ * uz_conv5x5: y[p][n] = sum_{tap, c} x[p + tap][c] * w[n][tap * Cin + c] + bias[n]  (forward: UZ_PACK_CONV_FWD weights;
+ * input gradient: the gradient as x and UZ_PACK_CONV_DGRAD weights).  Cin a multiple of 16 bytes and <= 512, Nout <= 512 of
+ * any value (the num_classes-wide output layer); everything else is refused with UZ_EINVAL before any launch.
+ * stats (nullable): BatchNorm partial rows [uz_conv5x5_grid_m()][2][Nout] of the stored values, as uz_conv_igemm leaves them.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct uz_conv5x5_desc {
+  int dtype;
+  int N, H, W;
+  int Cin, ldx;
+  int Nout, ldy;
+  int ksize;   /* 5 or 1 */
+} uz_conv5x5_desc;
+int uz_conv5x5_grid_m(const uz_conv5x5_desc* d);
+int uz_conv5x5(const uz_conv5x5_desc* d, const void* x, const void* w_packed, const float* bias, void* y, float* stats,
+               void* stream);
+/* out[i][j][tap] = sum_p L[p][i] * R[p + tap][j] for i < CiOut, j < CjOut: fp32, the (Cout, Cin, k, k) parameter layout with
+ * L = the output gradient and R = the layer input.  Ci, Cj: the operands' channel counts (multiples of 16 bytes, <= 512;
+ * a thin layer's operand is zero-padded to that), CiOut <= Ci, CjOut <= Cj: the parameter's.  Deterministic: per-range
+ * slabs in the workspace, summed in a fixed order. */
+typedef struct uz_wgrad5x5_desc {
+  int dtype;
+  int N, H, W;
+  int Ci, ldl;
+  int Cj, ldr;
+  int ksize;   /* 5 or 1 */
+  int CiOut, CjOut;
+} uz_wgrad5x5_desc;
+long long uz_wgrad5x5_workspace_bytes(const uz_wgrad5x5_desc* d);
+int uz_wgrad5x5(const uz_wgrad5x5_desc* d, const void* L, const void* R, float* out, void* workspace, void* stream);
+
+/* ContBatchNorm2d -> ELU with VNet's residual sums and Dropout2d masks (vnet.py:35, :65, :82-85, :102-114):
+ *   out  = act2( act1( x * scale + shift ) + res ),  act = ELU(alpha = 1) or identity: flags bit 0 = act1, bit 1 = act2
+ *   out2 = out * mask2[n][c]      (nullable: the Dropout2d'ed copy, e.g. straight into its half of a concat buffer;
+ *                                  mask2 fp32 (N, C) holding 0 or 1 / (1 - p))
+ * Any C; 16-byte vectors where C and every leading dimension allow them, and then every tensor must start on a 16-byte
+ * boundary (UZ_EINVAL otherwise; the same holds for the two backward passes). */
+int uz_bn_elu_apply(int dtype, const void* x, int ldx, const float* scale, const float* shift, int N, int HW, int C,
+                    const void* res, int ldres, void* out, int ldo, void* out2, int ldo2, const float* mask2, int flags,
+                    void* stream);
+/* Its backward, two passes as uz_bn_relu_bwd_*: G = g0 [+ g1] [+ g2 * mask2] is the gradient of `out` (g2: that of out2);
+ * no pre-activation tensor is kept: ELU'(z) = 1 where the stored result y > 0, else y + 1 (act2, from `out`), and act1's
+ * factor is recomputed from x.  reduce: partial rows [uz_bn_elu_bwd_rows()][2][C] of (sum dbn, sum dbn * xhat), which
+ * uz_bn_bwd_finalize() totals; apply: dx (gradient of x, batch statistics) and gres (nullable: gradient of res). */
+typedef struct uz_bn_elu_bwd_desc {
+  int dtype;
+  int N, HW, C;
+  int ldx, ldo, ldg0, ldg1, ldg2, lddx, ldgres;
+  int flags;
+} uz_bn_elu_bwd_desc;
+int uz_bn_elu_bwd_rows(const uz_bn_elu_bwd_desc* d);
+int uz_bn_elu_bwd_reduce(const uz_bn_elu_bwd_desc* d, const void* x, const void* out, const void* g0, const void* g1,
+                         const void* g2, const float* mask2, const float* scale, const float* shift, const float* mean,
+                         const float* invstd, float* partials, void* stream);
+int uz_bn_elu_bwd_apply(const uz_bn_elu_bwd_desc* d, const void* x, const void* out, const void* g0, const void* g1,
+                        const void* g2, const float* mask2, const float* scale, const float* shift, const float* mean,
+                        const float* invstd, const double* sums, void* dx, void* gres, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

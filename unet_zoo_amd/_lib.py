@@ -51,6 +51,8 @@ EXPORTS = (
     "uz_gemm_nt", "uz_softmax_fwd", "uz_softmax_bwd", "uz_adaptive_avgpool_fwd", "uz_adaptive_avgpool_bwd",
     "uz_rowdot_f32", "uz_cast_rows", "uz_wgrad_batched_workspace_bytes", "uz_wgrad_batched", "uz_wgrad_batched2",
     "uz_softmax_workspace_bytes", "uz_add_map", "uz_dropout", "uz_chanscale_relu", "uz_chanattn_probs_fwd", "uz_chanattn_probs_bwd",
+    "uz_conv5x5_grid_m", "uz_conv5x5", "uz_wgrad5x5_workspace_bytes", "uz_wgrad5x5",
+    "uz_bn_elu_apply", "uz_bn_elu_bwd_rows", "uz_bn_elu_bwd_reduce", "uz_bn_elu_bwd_apply",
 )
 
 
@@ -63,6 +65,21 @@ class ConvDesc(Structure):
 class WgradDesc(Structure):
     _fields_ = [(n, c_int) for n in (
         "dtype", "N", "H", "W", "Hr", "Wr", "Ci", "ldl", "Cj", "ldr", "ntaps", "taps_mode", "dil")]
+
+
+class Conv5Desc(Structure):
+    """uz_conv5x5_desc"""
+    _fields_ = [(n, c_int) for n in ("dtype", "N", "H", "W", "Cin", "ldx", "Nout", "ldy", "ksize")]
+
+
+class Wgrad5Desc(Structure):
+    """uz_wgrad5x5_desc"""
+    _fields_ = [(n, c_int) for n in ("dtype", "N", "H", "W", "Ci", "ldl", "Cj", "ldr", "ksize", "CiOut", "CjOut")]
+
+
+class BnEluBwdDesc(Structure):
+    """uz_bn_elu_bwd_desc"""
+    _fields_ = [(n, c_int) for n in ("dtype", "N", "HW", "C", "ldx", "ldo", "ldg0", "ldg1", "ldg2", "lddx", "ldgres", "flags")]
 
 
 class BnBwdDesc(Structure):
@@ -288,6 +305,14 @@ def load():
     lib.uz_adaptive_avgpool_bwd.argtypes = [ip, vp, ip, ip, ip, ip, ip, vp, ip, ip, ip, ip, vp]
     lib.uz_rowdot_f32.argtypes = [ip, vp, ip, vp, ip, ll, ip, vp, vp]
     lib.uz_cast_rows.argtypes = [ip, vp, ip, vp, ip, ll, ip, ip, vp]
+    lib.uz_conv5x5_grid_m.argtypes = [POINTER(Conv5Desc)]
+    lib.uz_conv5x5.argtypes = [POINTER(Conv5Desc), vp, vp, vp, vp, vp, vp]
+    lib.uz_wgrad5x5_workspace_bytes.argtypes = [POINTER(Wgrad5Desc)]
+    lib.uz_wgrad5x5.argtypes = [POINTER(Wgrad5Desc), vp, vp, vp, vp, vp]
+    lib.uz_bn_elu_apply.argtypes = [ip, vp, ip, vp, vp, ip, ip, ip, vp, ip, vp, ip, vp, ip, vp, ip, vp]
+    lib.uz_bn_elu_bwd_rows.argtypes = [POINTER(BnEluBwdDesc)]
+    lib.uz_bn_elu_bwd_reduce.argtypes = [POINTER(BnEluBwdDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.uz_bn_elu_bwd_apply.argtypes = [POINTER(BnEluBwdDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("uz_last_error_string", "uz_source_hash"):

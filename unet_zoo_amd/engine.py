@@ -2052,6 +2052,113 @@ class Engine:
             self._heads.append((bwd, 1))
         return logits
 
+    # ------------------------------------------------------------------ VNet blocks (vnet.py; uz_conv5x5.hip)
+    def conv5x5(self, x: Act, conv: nn.Conv2d) -> Tuple[Act, torch.Tensor]:
+        """Conv2d(k5, padding 2, stride 1, bias) in front of an always-batch-statistics BatchNorm (LUConv.conv1,
+        OutputTransition.conv1; vnet.py:31, :120): returns the raw output and its BatchNorm partial sums.  The bias is
+        added (so the running mean includes it) and its gradient is the analytic zero.  An output narrower than 8 channels
+        (num_classes) lives in a zero-padded 8-column buffer, and so does its gradient (bn_elu(pad_grad=True)): the two
+        gradient kernels read 16-byte vectors."""
+        assert conv.kernel_size == (5, 5) and conv.padding == (2, 2) and conv.stride == (1, 1) and conv.dilation == (1, 1) \
+            and conv.groups == 1 and conv.in_channels == x.C
+        N, H, W, Cout = x.N, x.H, x.W, conv.out_channels
+        thin = Cout % 8 != 0
+        if thin:
+            y = Act(torch.zeros((x.P, _round_up(Cout, 8)), dtype=self.dtype, device=self.device), 0, Cout, N, H, W)
+        else:
+            y = self.new_act(N, H, W, Cout)
+        stats = ops.conv5x5(x, self._pack(conv.weight, L.PACK_CONV_FWD), conv.bias.detach() if conv.bias is not None else None,
+                            y, want_stats=True)
+        if self.record:
+            def bwd():
+                g = self._total_grad(y)
+                if g is None:
+                    return
+                if conv.bias is not None:
+                    self._give_grad(conv.bias, None)     # a batch-statistics BatchNorm follows: analytically zero
+                if thin:                                 # the zero-padded buffer as a whole
+                    assert g.off == 0 and g.ld == _round_up(Cout, 8)
+                    g = Act(g.buf, 0, g.ld, N, H, W)
+                self._give_grad(conv.weight, ops.wgrad5x5(g, x, tuple(conv.weight.shape), out=self._dst(conv.weight)))
+                if x.needs_grad:
+                    if thin:    # [ci][(24 - t) * 8 + co], zero for co >= Cout: num_classes x 800 numbers, torch's job
+                        wd = torch.zeros((x.C, 25, g.C), dtype=torch.float32, device=self.device)
+                        wd[:, :, :Cout] = conv.weight.detach().flip(2, 3).reshape(Cout, x.C, 25).permute(1, 2, 0)
+                        wd = wd.reshape(x.C, 25 * g.C).to(self.dtype)
+                    else:
+                        wd = self._pack(conv.weight, L.PACK_CONV_DGRAD)
+                    dx = self.new_act(N, H, W, x.C)
+                    ops.conv5x5(g, wd, None, dx)
+                    x.add_grad(dx)
+
+            self.tape.append(bwd)
+        return y, stats
+
+    def bn_elu(self, raw: Act, bn: nn.Module, stats: Optional[torch.Tensor] = None, *, act1: bool = True, act2: bool = False,
+               res: Optional[Act] = None, out: Optional[Act] = None, out2: Optional[Act] = None,
+               mask2: Optional[torch.Tensor] = None, pad_grad: bool = False) -> Act:
+        """ContBatchNorm2d -> ELU of a raw convolution output with VNet's sums and masks in the same pass:
+        out = act2(act1(bn(raw)) + res), out2 = out * mask2[n, c] (vnet.py:35, :65, :82-85, :102-114).  The BatchNorm uses
+        BATCH statistics and updates the running ones in eval mode as well, and never counts its batches (vnet.py:21-25).
+        stats: the partial sums of `raw` if its convolution left them, else one statistics pass is run.  out / out2 may be
+        slots of a concat buffer.  pad_grad: raw is a zero-padded thin buffer (conv5x5), and so is its gradient."""
+        N, H, W, C = raw.N, raw.H, raw.W, raw.C
+        if raw.P <= 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {(N, C, H, W)}")
+        if stats is None:
+            stats = ops.colstats(raw)
+        mom = bn.momentum if bn.momentum is not None else 0.1
+        vec = ops.bn_finalize(stats, raw.P, bn.weight.detach(), bn.bias.detach(), bn.eps, mom, bn.running_mean, bn.running_var)
+        if out is None:
+            out = Act(torch.zeros_like(raw.buf), 0, C, N, H, W) if pad_grad else self.new_act(N, H, W, C)
+        ops.bn_elu_apply(raw, vec[0], vec[1], out, act1=act1, act2=act2, res=res, out2=out2, mask2=mask2)
+        if self.record:
+            self._bn_channels += C
+
+            def bwd():
+                gs = self._sum_grads(out, 2)
+                g2 = self._sum_grads(out2, 1)[0] if (out2 is not None and out2.grads) else None
+                if not gs and g2 is None:
+                    return
+                if not gs:      # only the masked copy was read
+                    z = self.new_act(N, H, W, C)
+                    z.buf.zero_()
+                    gs = [z]
+                if pad_grad:
+                    dx = Act(torch.zeros_like(raw.buf), 0, C, N, H, W)
+                else:
+                    dx = self.new_act(N, H, W, C)
+                gres = self.new_act(N, H, W, C) if (res is not None and res.needs_grad) else None
+                dgamma, dbeta = self._dst(bn.weight), self._dst(bn.bias)
+                if dgamma is None:
+                    dgamma = torch.empty(C, dtype=torch.float32, device=self.device)
+                if dbeta is None:
+                    dbeta = torch.empty(C, dtype=torch.float32, device=self.device)
+                ops.bn_elu_bwd(raw, vec, out, gs[0], gs[1] if len(gs) > 1 else None, g2, mask2, self._bn_sums(C), dx, gres,
+                               dgamma, dbeta, act1=act1, act2=act2)
+                self._give_grad(bn.weight, dgamma)
+                self._give_grad(bn.bias, dbeta)
+                if gres is not None:
+                    res.add_grad(gres)
+                if raw.needs_grad:
+                    raw.add_grad(dx)
+
+            self.tape.append(bwd)
+        return out
+
+    def logits_from(self, x: Act) -> torch.Tensor:
+        """an activation as the model output (N, C, H, W) fp32 (OutputTransition ends in BatchNorm -> ELU, vnet.py:125); its
+        gradient comes back as a zero-padded buffer of x's row length"""
+        logits = x.buf[:, x.off:x.off + x.C].float().reshape(x.N, x.H, x.W, x.C).permute(0, 3, 1, 2).contiguous()
+        if self.record:
+            def bwd(g_logits: torch.Tensor):
+                gb = torch.zeros((x.P, x.ld), dtype=self.dtype, device=self.device)
+                gb[:, :x.C] = g_logits.permute(0, 2, 3, 1).reshape(x.P, x.C)
+                x.add_grad(Act(gb, 0, x.C, x.N, x.H, x.W))
+
+            self._heads.append((bwd, 1))
+        return logits
+
     # ------------------------------------------------------------------ backward
     def backward(self, grad_outputs: Sequence[Optional[torch.Tensor]]) -> Dict[nn.Parameter, torch.Tensor]:
         """Run the recorded tape in reverse.  `grad_outputs` pairs with the out_conv heads in

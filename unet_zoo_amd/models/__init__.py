@@ -25,6 +25,7 @@ from .unet_transformer import U_Transformer
 from .multiresunet import MultiResUnet
 from .uctransnet import UCTransNet, get_uctransnet_config
 from .unext import UNext, UNext_S
+from .vnet import VNet
 
 # every name the reference registers (models/__init__.py:27-52); value = constructor or None
 _model_entries: Dict[str, Optional[Callable[..., nn.Module]]] = {
@@ -38,7 +39,7 @@ _model_entries: Dict[str, Optional[Callable[..., nn.Module]]] = {
     'multiresunet': MultiResUnet,
     'nested_unet': NestedUNet,
     'missformer': MISSFormer,
-    'vnet': None,
+    'vnet': VNet,
     'u2net': U2NET,
     'u2netp': U2NETP,
     'swin_unet_v2': SwinTransformerSys,
@@ -135,6 +136,9 @@ def create_model(model_name: str, pretrained: bool = False, **kwargs) -> nn.Modu
                            ('qk_scale', None), ('drop_rate', 0.0), ('attn_drop_rate', 0.0), ('drop_path_rate', 0.0),
                            ('norm_layer', nn.LayerNorm), ('depths', None), ('sr_ratios', None)):
             args[k] = kwargs.pop(k, default)
+    elif name == 'vnet':
+        # models/__init__.py:150-154
+        args.update(elu=kwargs.pop('elu', True), nll=kwargs.pop('nll', False), in_channels=in_channels, num_classes=num_classes)
     else:
         args.update(in_channels=in_channels, num_classes=num_classes)
     args.update(kwargs)  # leftovers reach the constructor: unknown ones raise TypeError there
@@ -145,4 +149,4 @@ def create_model(model_name: str, pretrained: bool = False, **kwargs) -> nn.Modu
     return model
 
 
-__all__ = ['UNet', 'AttentionUNet', 'U2NET', 'U2NETP', 'SwinTransformerSys', 'NestedUNet', 'ResUnet', 'MISSFormer', 'TransAttUNet', 'U_Transformer', 'MultiResUnet', 'UCTransNet', 'UNext', 'UNext_S', 'list_models', 'hip_models', 'get_model_config', 'create_model']
+__all__ = ['UNet', 'AttentionUNet', 'U2NET', 'U2NETP', 'SwinTransformerSys', 'NestedUNet', 'ResUnet', 'MISSFormer', 'TransAttUNet', 'U_Transformer', 'MultiResUnet', 'UCTransNet', 'UNext', 'UNext_S', 'VNet', 'list_models', 'hip_models', 'get_model_config', 'create_model']

@@ -1417,3 +1417,85 @@ def chanscale_relu(mode: int, g: Optional[Act], x: Act, s: Optional[torch.Tensor
         L.check(L.load().uz_chanscale_relu(L.dtype_code(x.dtype), mode, g.ptr() if g is not None else None, g.ld if g is not None else 0,
                                            x.ptr(), x.ld, _p(s), _p(a), x.N, x.H * x.W, x.C, out.ptr(), out.ld, L.stream_ptr()),
                 "uz_chanscale_relu")
+
+
+# ---- VNet: k = 5 (or 1) convolution and the BatchNorm + ELU passes (uz_conv5x5.hip) -----------------------------------------
+def conv5x5(x: Act, w_packed: torch.Tensor, bias: Optional[torch.Tensor], y: Act, *, ksize: int = 5,
+            want_stats: bool = False) -> Optional[torch.Tensor]:
+    """y = conv_k(x, w) + bias, k = 5 (zero padding 2) or 1, stride 1; w_packed [y.C][k*k*x.C] (PACK_CONV_FWD, or
+    PACK_CONV_DGRAD with the output gradient as x for the input gradient).  y.C may be any number <= 512 (the library
+    refuses the rest).  Returns the BatchNorm partial-sum rows of y if asked."""
+    L.require_cuda(x.buf, w_packed, y.buf)
+    lib = L.load()
+    d = L.Conv5Desc(L.dtype_code(x.dtype), x.N, x.H, x.W, x.C, x.ld, y.C, y.ld, ksize)
+    assert w_packed.dtype == x.dtype == y.dtype and w_packed.is_contiguous()
+    assert tuple(w_packed.shape) == (y.C, ksize * ksize * x.C), (tuple(w_packed.shape), y.C, ksize, x.C)
+    assert (y.N, y.H, y.W) == (x.N, x.H, x.W)
+    gm = L.check_count(lib.uz_conv5x5_grid_m(byref(d)), "uz_conv5x5_grid_m")
+    stats = torch.empty((gm, 2, y.C), dtype=torch.float32, device=x.buf.device) if want_stats else None
+    K, es = ksize * ksize * x.C, x.buf.element_size()
+    with _Timed(f"conv{ksize}x{ksize}_{_tname(x.dtype)}", 2.0 * x.P * y.C * K, es * (x.P * x.C + x.P * y.C + y.C * K)):
+        L.check(lib.uz_conv5x5(byref(d), x.ptr(), w_packed.data_ptr(), _p(bias), y.ptr(), _p(stats), L.stream_ptr()),
+                "uz_conv5x5")
+    return stats
+
+
+def wgrad5x5(Lt: Act, Rt: Act, out_shape, *, ksize: int = 5, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[i, j, tap] = sum_p L[p, i] * R[p + tap, j] for i < out_shape[0], j < out_shape[1] (fp32, the Conv2d parameter
+    layout); the operands may be wider than that (a thin layer's zero-padded gradient)."""
+    L.require_cuda(Lt.buf, Rt.buf)
+    lib = L.load()
+    d = L.Wgrad5Desc(L.dtype_code(Lt.dtype), Lt.N, Lt.H, Lt.W, Lt.C, Lt.ld, Rt.C, Rt.ld, ksize, out_shape[0], out_shape[1])
+    assert (Lt.N, Lt.H, Lt.W) == (Rt.N, Rt.H, Rt.W) and Lt.dtype == Rt.dtype
+    wsb = L.check_count(lib.uz_wgrad5x5_workspace_bytes(byref(d)), "uz_wgrad5x5_workspace_bytes")
+    ws = torch.empty(wsb // 4, dtype=torch.float32, device=Lt.buf.device)
+    if out is None:
+        out = torch.empty(tuple(out_shape), dtype=torch.float32, device=Lt.buf.device)
+    assert out.numel() == out_shape[0] * out_shape[1] * ksize * ksize and out.is_contiguous() and out.dtype == torch.float32
+    with _Timed(f"wgrad{ksize}x{ksize}_{_tname(Lt.dtype)}", 2.0 * Lt.P * Lt.C * Rt.C * ksize * ksize,
+                Lt.buf.element_size() * (Lt.P * Lt.C + Rt.P * Rt.C) + 2.0 * wsb):
+        L.check(lib.uz_wgrad5x5(byref(d), Lt.ptr(), Rt.ptr(), out.data_ptr(), ws.data_ptr(), L.stream_ptr()), "uz_wgrad5x5")
+    return out
+
+
+def bn_elu_apply(x: Act, scale: torch.Tensor, shift: torch.Tensor, out: Act, *, act1: bool = True, act2: bool = False,
+                 res: Optional[Act] = None, out2: Optional[Act] = None, mask2: Optional[torch.Tensor] = None) -> None:
+    """out = act2(act1(x * scale + shift) + res), act = ELU or identity; out2 = out * mask2[n, c] (a Dropout2d'ed copy)."""
+    assert (out.P, out.C) == (x.P, x.C) and (res is None or (res.P, res.C) == (x.P, x.C))
+    assert (out2 is None) == (mask2 is None)
+    if out2 is not None:
+        assert (out2.P, out2.C) == (x.P, x.C) and tuple(mask2.shape) == (x.N, x.C) and mask2.dtype == torch.float32 \
+            and mask2.is_contiguous()
+    es = x.buf.element_size()
+    with _Timed("bn_elu_apply", 0.0, es * x.P * x.C * (2 + (res is not None) + (out2 is not None))):
+        L.check(L.load().uz_bn_elu_apply(
+            L.dtype_code(x.dtype), x.ptr(), x.ld, scale.data_ptr(), shift.data_ptr(), x.N, x.H * x.W, x.C,
+            res.ptr() if res is not None else None, res.ld if res is not None else 0, out.ptr(), out.ld,
+            out2.ptr() if out2 is not None else None, out2.ld if out2 is not None else 0, _p(mask2),
+            int(act1) | (2 if act2 else 0), L.stream_ptr()), "uz_bn_elu_apply")
+
+
+def bn_elu_bwd(x: Act, vec: torch.Tensor, out: Act, g0: Act, g1: Optional[Act], g2: Optional[Act],
+               mask2: Optional[torch.Tensor], sums: torch.Tensor, dx: Act, gres: Optional[Act], dgamma: torch.Tensor,
+               dbeta: torch.Tensor, *, act1: bool, act2: bool) -> None:
+    """Two-pass backward of bn_elu_apply (batch statistics): vec = (scale, shift, mean, invstd) of the forward, g0 / g1 the
+    gradients of out, g2 that of out2; writes dx (gradient of x), gres (gradient of res), dgamma, dbeta.  `sums`: float64
+    (2, C) scratch."""
+    lib = L.load()
+    d = L.BnEluBwdDesc(L.dtype_code(x.dtype), x.N, x.H * x.W, x.C, x.ld, out.ld, g0.ld, g1.ld if g1 is not None else 0,
+                       g2.ld if g2 is not None else 0, dx.ld, gres.ld if gres is not None else 0,
+                       int(act1) | (2 if act2 else 0))
+    rows = L.check_count(lib.uz_bn_elu_bwd_rows(byref(d)), "uz_bn_elu_bwd_rows")
+    part = torch.empty((rows, 2, x.C), dtype=torch.float32, device=x.buf.device)
+    args = (x.ptr(), out.ptr(), g0.ptr(), g1.ptr() if g1 is not None else None, g2.ptr() if g2 is not None else None,
+            _p(mask2) if g2 is not None else None, vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(), vec[3].data_ptr())
+    s = L.stream_ptr()
+    nsrc = 2 + (g1 is not None) + (g2 is not None) + int(act2)
+    es = x.buf.element_size()
+    with _Timed("bn_elu_bwd_reduce", 0.0, es * x.P * x.C * nsrc):
+        L.check(lib.uz_bn_elu_bwd_reduce(byref(d), *args, part.data_ptr(), s), "uz_bn_elu_bwd_reduce")
+    L.check(lib.uz_bn_bwd_finalize(part.data_ptr(), rows, x.C, sums.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), s),
+            "uz_bn_bwd_finalize")
+    with _Timed("bn_elu_bwd_apply", 0.0, es * x.P * x.C * (nsrc + 1 + (gres is not None))):
+        L.check(lib.uz_bn_elu_bwd_apply(byref(d), *args, sums.data_ptr(), dx.ptr(), gres.ptr() if gres is not None else None, s),
+                "uz_bn_elu_bwd_apply")
