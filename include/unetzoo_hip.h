@@ -257,6 +257,16 @@ int uz_conv3x3_first_fwd(int dtype, const float* x, int N, int C, int H, int W, 
 long long uz_conv3x3_first_wgrad_workspace_bytes(int N, int H, int W, int Cout);
 int uz_conv3x3_first_wgrad(int dtype, const float* x, int N, int C, int H, int W, const void* dy, int lddy, int Cout, float* dw,
                            void* workspace, void* stream);
+/* uz_conv3x3_first_wgrad reading its dy THROUGH the BatchNorm + ReLU backward of the layer (training, no pool, no residual):
+ * the image needs no input gradient, so the weight gradient is the only reader of that dy and forms it where it fills its
+ * tile, from the gradient g of the activation and the raw convolution output y (both bf16 NHWC), the four BatchNorm vectors
+ * and the totals sums[2][C] of uz_bn_bwd_finalize, with the expressions of uz_bn_relu_bwd_apply, rounded to bf16:
+ *   k0 = (float)(sums[0][c] / count), k1 = (float)(sums[1][c] / count), dz = fma(y, scale, shift) > 0 ? g : 0,
+ *   dy = bf16(scale * (dz - k0 - (y - mean) * invstd * k1)).
+ * Same workspace and reduction: dw is bitwise that of uz_bn_relu_bwd_apply + uz_conv3x3_first_wgrad. */
+int uz_conv3x3_first_wgrad_bn(int dtype, const float* x, int N, int C, int H, int W, const void* g, int ldg, const void* y,
+                              int ldy, const float* scale, const float* shift, const float* mean, const float* invstd,
+                              const double* sums, double count, int Cout, float* dw, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Weight re-packing: fp32 master parameters in the reference layout -> kernel layout in run dtype.
@@ -391,6 +401,15 @@ int uz_bn_relu_bwd_apply_fin(const uz_bnbwd_desc* d, const void* y, const float*
 /* The finalize half of uz_bn_relu_bwd_reduce() alone: sums[2][C] (double), dbeta = sums[0], dgamma = sums[1] from
  * `rows` partial rows [rows][2][C] written by uz_conv_igemm_bnred(). */
 int uz_bn_bwd_finalize(const float* partial, int rows, int C, double* sums, float* dgamma, float* dbeta, void* stream);
+/* uz_bn_relu_bwd_apply for the block in front of the 1x1 head when its gradient was never written down (bf16, ReLU, no pool;
+ * uz_outconv_bwd_bnred with dx == NULL): the gradient of pixel p, channel c is formed from the logit gradients g (fp32 NKHW)
+ * and the head's weights w[Kout][C] as the head would have stored it -- d = 0; d = fmaf(g[n][k][hw], w[k][c], d) for
+ * ascending k; bf16(d) -- and enters the expressions of the apply pass unchanged: same dy, bit for bit, as the two launches.
+ * d->pool_ceil: bit 2 (walk from the end) only; ldg0 / ldg1 / ldgp unused. */
+int uz_bn_relu_bwd_apply_head_supported(int dtype, int C, int Kout);
+int uz_bn_relu_bwd_apply_head(const uz_bnbwd_desc* d, const void* y, const float* scale, const float* shift, const float* mean,
+                              const float* invstd, const float* g_nchw, const float* w, int Kout, const double* sums,
+                              double count, void* dy, void* stream);
 
 /* 1x1 convolution with few outputs (OutConv, common_layers.py:125), NCHW fp32 logits.
  *   out[n, k, h, w] = b[k] + sum_c x[p, c] * w[k, c],  k < Kout <= 8 */
@@ -411,7 +430,8 @@ int uz_outconv_bwd(int dtype, const void* x, int ldx, int N, int HW, int C, cons
 /* uz_outconv_bwd with the first pass of a BatchNorm backward in the same pass over the pixels (bf16): x = relu(bn(bn_y))
  * feeds only this head, so the gradient dx it writes is the whole gradient of that activation; bn_partial receives
  * [uz_outconv_bwd_rows()][2][C] partial rows for uz_bn_bwd_finalize() (see uz_conv_igemm_bnred).  x == NULL: the
- * activation was never written down (uz_outconv_fwd_xf); the kernel forms it from bn_y, scale, shift (ldx unused). */
+ * activation was never written down (uz_outconv_fwd_xf); the kernel forms it from bn_y, scale, shift (ldx unused).
+ * dx == NULL: the gradient is not stored (its reader forms it: uz_bn_relu_bwd_apply_head); dw, db and the rows as before. */
 int uz_outconv_bwd_rows(int dtype, int N, int HW, int C);
 int uz_outconv_bwd_bnred(int dtype, const void* x, int ldx, int N, int HW, int C, const float* w, int Kout,
                          const float* g_nchw, void* dx, int lddx, float* dw, float* db, void* workspace,

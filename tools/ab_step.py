@@ -1,6 +1,6 @@
 """A/B timing of the graphed UNet step in ONE process on ONE box (boxes differ by +-10 % on the MFMA kernels, so
 separate runs cannot resolve a 1 % change): every variant = (name, {Engine class attribute: value}), measured interleaved.
-   python tools/ab_step.py [--model unet] [--rounds 3]"""
+   python tools/ab_step.py [--model unet] [--rounds 3] [--only shipped,"head gradient written"]"""
 import argparse
 import os
 import sys
@@ -11,8 +11,11 @@ import unet_zoo_amd
 from unet_zoo_amd.engine import Engine
 
 _ON = dict(BN_BWD_ALTERNATE=True, reverse_element_passes=True, fuse_bn_finalize=False, fold_bn_apply=True, fold_bn_apply_head=True,
-           fuse_bn_reduce=True, fuse_bn_reduce_convt=True)
+           fuse_bn_reduce=True, fuse_bn_reduce_convt=True, fold_head_grad=True, fold_first_bn_bwd=True)
 VARIANTS = [("shipped", dict(_ON)),
+            ("head gradient written", dict(_ON, fold_head_grad=False)),
+            ("first layer: dy written", dict(_ON, fold_first_bn_bwd=False)),
+            ("head gradient and first dy written", dict(_ON, fold_head_grad=False, fold_first_bn_bwd=False)),
             ("head: apply pass kept", dict(_ON, fold_bn_apply_head=False)),
             ("bwd passes not alternating", dict(_ON, BN_BWD_ALTERNATE=False)),
             ("element passes ascending", dict(_ON, BN_BWD_ALTERNATE=False, reverse_element_passes=False)),
@@ -52,8 +55,13 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--tunes", default=None, help="comma list of UZ_TUNE values instead of the Engine variants (ablation build)")
+    ap.add_argument("--only", default=None, help="comma list of variant names to time (default: all)")
     a = ap.parse_args()
     global VARIANTS
+    if a.only:
+        names = a.only.split(",")
+        assert all(any(n == v[0] for v in VARIANTS) for n in names), names
+        VARIANTS = [v for v in VARIANTS if v[0] in names]
     if a.tunes:
         VARIANTS = [(f"UZ_TUNE={t}", {"UZ_TUNE": int(t)}) for t in a.tunes.split(",")]
     built = [(name, build(attrs, a.model, a.batch, a.size)) for name, attrs in VARIANTS]

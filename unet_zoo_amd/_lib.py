@@ -26,9 +26,9 @@ LIB_PATH = os.environ.get("UNET_ZOO_AMD_LIB") or os.path.join(os.path.dirname(os
 EXPORTS = (
     "uz_abi_version", "uz_last_error_string", "uz_build_ablate", "uz_source_hash", "uz_set_cu_reserve", "uz_get_cu_reserve", "uz_clock_probe", "uz_conv_igemm_grid_m", "uz_conv_igemm",
     "uz_wgrad_split", "uz_wgrad_workspace_bytes", "uz_wgrad", "uz_wgrad_kernel_name", "uz_wgrad_phase", "uz_wgrad_xf_supported", "uz_wgrad_xf", "uz_conv3x3_first_supported", "uz_conv3x3_first_rows", "uz_conv3x3_first_fwd",
-    "uz_conv3x3_first_wgrad_workspace_bytes", "uz_conv3x3_first_wgrad", "uz_pack_weights", "uz_pack_weights_batched", "uz_pack_conv3x3_batched", "uz_im2col3x3_nchw", "uz_bn_finalize",
+    "uz_conv3x3_first_wgrad_workspace_bytes", "uz_conv3x3_first_wgrad", "uz_conv3x3_first_wgrad_bn", "uz_pack_weights", "uz_pack_weights_batched", "uz_pack_conv3x3_batched", "uz_im2col3x3_nchw", "uz_bn_finalize",
     "uz_bn_eval_scale", "uz_bn_relu_apply", "uz_bn_relu_bwd_workspace_bytes", "uz_bn_relu_bwd_reduce", "uz_bn_relu_bwd_apply",
-    "uz_outconv_fwd", "uz_outconv_fwd_xf", "uz_outconv_bwd_workspace_bytes", "uz_outconv_bwd", "uz_outconv_bwd_rows", "uz_outconv_bwd_bnred",
+    "uz_outconv_fwd", "uz_outconv_fwd_xf", "uz_outconv_bwd_workspace_bytes", "uz_outconv_bwd", "uz_outconv_bwd_rows", "uz_outconv_bwd_bnred", "uz_bn_relu_bwd_apply_head_supported", "uz_bn_relu_bwd_apply_head",
     "uz_colsum",
     "uz_attn_grid", "uz_attn_psi_fwd", "uz_attn_gate_fwd", "uz_attn_bwd_psi", "uz_attn_bwd_reduce",
     "uz_attn_bwd_apply", "uz_sum_rows", "uz_sum_rows_f32", "uz_sum2x2",
@@ -216,6 +216,7 @@ def load():
     lib.uz_conv3x3_first_wgrad_workspace_bytes.argtypes = [ip, ip, ip, ip]
     lib.uz_conv3x3_first_wgrad_workspace_bytes.restype = ctypes.c_longlong
     lib.uz_conv3x3_first_wgrad.argtypes = [ip, vp, ip, ip, ip, ip, vp, ip, ip, vp, vp, vp]
+    lib.uz_conv3x3_first_wgrad_bn.argtypes = [ip, vp, ip, ip, ip, ip, vp, ip, vp, ip, vp, vp, vp, vp, vp, ctypes.c_double, ip, vp, vp, vp]
     lib.uz_pack_weights.argtypes = [ip, ip, vp, ip, ip, ip, ip, vp, vp]
     lib.uz_pack_weights_batched.argtypes = [ip, vp, ip, ctypes.c_longlong, vp]
     lib.uz_pack_conv3x3_batched.argtypes = [ip, vp, ip, ip, vp]
@@ -233,6 +234,8 @@ def load():
     lib.uz_outconv_bwd_workspace_bytes.argtypes = [ip, ip, ip, ip, ip]
     lib.uz_outconv_bwd.argtypes = [ip, vp, ip, ip, ip, ip, vp, ip, vp, vp, ip, vp, vp, vp, vp]
     lib.uz_outconv_bwd_rows.argtypes = [ip, ip, ip, ip]
+    lib.uz_bn_relu_bwd_apply_head_supported.argtypes = [ip, ip, ip]
+    lib.uz_bn_relu_bwd_apply_head.argtypes = [POINTER(BnBwdDesc), vp, vp, vp, vp, vp, vp, vp, ip, vp, ctypes.c_double, vp, vp]
     lib.uz_outconv_bwd_bnred.argtypes = [ip, vp, ip, ip, ip, ip, vp, ip, vp, vp, ip, vp, vp, vp, vp, ip, vp, vp, vp, vp, vp, vp]
     lib.uz_colsum.argtypes = [ip, vp, ip, ip, ip, vp, vp]
     lib.uz_colsum_workspace_bytes.argtypes = [ip, ip, ip]

@@ -32,6 +32,16 @@ struct CfArgs {
   const void* dy;
   float* slab;
   int N, C, H, W, Cout, ldy, th_n, tw_n, ntiles;
+  // weight gradient THROUGH the layer's BatchNorm + ReLU backward (uz_conv3x3_first_wgrad_bn): dy is then the gradient g of the
+  // activation, and the kernel forms the BatchNorm-backward output from it and the raw convolution output yraw
+  const void* yraw;
+  const float* bn_scale;
+  const float* bn_shift;
+  const float* bn_mean;
+  const float* bn_invstd;
+  const double* bn_sums;   // [2][Cout] totals (uz_bn_bwd_finalize)
+  double inv_count;
+  int ldyr;
 };
 
 __device__ __forceinline__ float round_bf16(float v) { return (float)(bf16_t)v; }
@@ -219,10 +229,15 @@ __global__ __launch_bounds__(256) void conv_first_fwd_kernel(const CfArgs a) {
 }
 
 // ---- weight gradient: persistent workgroups over tiles; wave w owns rows 2w, 2w + 1 of a tile (4 sub-steps of 16 pixels) ----
-template <int CT>
-__global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const CfArgs a) {
+// BN: a.dy holds the gradient g of the ACTIVATION; the dy of the product is the apply pass of the BatchNorm + ReLU backward
+// (bn_relu_bwd_kernel PASS 2, uz_eltwise.hip: same expressions, same order, rounded to bf16), formed where the tile is
+// stored to LDS from the raw g and y registers fetched one tile ahead -- that dy tensor (134 MB written and read back at
+// B = 16, 256 x 256 x 64) then never exists; the MFMAs see the same bf16 operands
+template <int CT, bool BN>
+__device__ __forceinline__ void conv_first_wgrad_body(const CfArgs& a) {
   constexpr int RB = CT * 64;                       // bytes per dy pixel row in LDS
   __shared__ float sx[3 * PH * PW];
+  __shared__ __attribute__((aligned(16))) float sbn[BN ? 6 : 1][64];   // scale, shift, mean, invstd, k0, k1
   __shared__ __attribute__((aligned(16))) char sdy[TH * TW * RB];
   static_assert(4 * CT * 16 * 64 * 4 == TH * TW * RB, "the waves' accumulators meet in the dy tile's LDS");
   float (*sacc)[CT][16][64] = reinterpret_cast<float (*)[CT][16][64]>(sdy);
@@ -231,6 +246,18 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const CfArgs a) {
   const int per = a.th_n * a.tw_n;
   const int K = a.C * 9;
   const bf16_t* dyg = static_cast<const bf16_t*>(a.dy);
+  const bf16_t* yrg = static_cast<const bf16_t*>(a.yraw);
+  if constexpr (BN) {
+    if (tid < 64) {
+      const int c = tid < a.Cout ? tid : 0;
+      sbn[0][tid] = a.bn_scale[c];
+      sbn[1][tid] = a.bn_shift[c];
+      sbn[2][tid] = a.bn_mean[c];
+      sbn[3][tid] = a.bn_invstd[c];
+      sbn[4][tid] = (float)(a.bn_sums[c] * a.inv_count);
+      sbn[5][tid] = (float)(a.bn_sums[a.Cout + c] * a.inv_count);
+    }
+  }
 
   // patch fragment: lane (k = lane % 32 -> (c, ty, tx), pixel block b): 8 consecutive pixels of one halo row
   const int k = l31;
@@ -250,7 +277,7 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const CfArgs a) {
   constexpr int CPP = RB / 16;                      // 16-byte chunks per dy pixel
   constexpr int NDY = TH * TW * CPP / 256;          // dy chunks per thread and tile (8 or 4)
   float hreg[4];
-  f32x4 dreg[NDY];
+  f32x4 dreg[NDY], yreg[BN ? NDY : 1];
   unsigned hmask = 0, dmask = 0;
   auto dy_fetch = [&](int tile) __attribute__((always_inline)) {
     const int img = tile / per, rem = tile - img * per;
@@ -263,6 +290,7 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const CfArgs a) {
       // unconditional (pixel 0 for a chunk outside the image / beyond the channels), RAW; zeroed where it is stored to LDS
       const bool ok = gh < a.H && gw < a.W && ch * 8 < a.Cout;
       dreg[j] = *reinterpret_cast<const f32x4*>(ok ? dyg + (((size_t)img * a.H + gh) * a.W + gw) * a.ldy + ch * 8 : dyg);
+      if constexpr (BN) yreg[j] = *reinterpret_cast<const f32x4*>(ok ? yrg + (((size_t)img * a.H + gh) * a.W + gw) * a.ldyr + ch * 8 : yrg);
       dmask |= ok ? 1u << j : 0u;
     }
   };
@@ -275,14 +303,48 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const CfArgs a) {
     __syncthreads();   // the previous tile is consumed
     halo_store(sx, hreg, hmask, tid, a.C * PH * PW);
     // dy tile, pixel-major [row][col][channel]; 64-byte granule swizzle on the way in
+    if constexpr (!BN) {
 #pragma unroll
-    for (int j = 0; j < NDY; ++j) {
-      const int idx = tid + 256 * j;
-      const int p = idx / CPP, ch = idx % CPP;
-      const int gran = ch >> 2, sw = (p >> 1) & 1;
-      const int pg = (CT == 2) ? (gran ^ sw) : gran;   // (one granule per pixel at CT = 1: nothing to swizzle)
-      const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-      *reinterpret_cast<f32x4*>(sdy + p * RB + pg * 64 + (ch & 3) * 16) = (dmask >> j & 1u) ? dreg[j] : z4;
+      for (int j = 0; j < NDY; ++j) {
+        const int idx = tid + 256 * j;
+        const int p = idx / CPP, ch = idx % CPP;
+        const int gran = ch >> 2, sw = (p >> 1) & 1;
+        const int pg = (CT == 2) ? (gran ^ sw) : gran;   // (one granule per pixel at CT = 1: nothing to swizzle)
+        const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+        *reinterpret_cast<f32x4*>(sdy + p * RB + pg * 64 + (ch & 3) * 16) = (dmask >> j & 1u) ? dreg[j] : z4;
+      }
+    } else {
+      // this thread's chunk is the same 8 channels for every j (256 % CPP == 0); the table was written in front of the barrier
+      // above.  Two halves of four channels, each with its own 24 constants: all 48 live beside the two prefetched tiles and
+      // the accumulators do not fit three workgroups per CU
+      typedef __attribute__((ext_vector_type(2))) float f32x2;
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        const int c4 = (tid % CPP) * 8 + 4 * hf;
+        const f32x4 bsc = *reinterpret_cast<const f32x4*>(&sbn[0][c4]), bsh = *reinterpret_cast<const f32x4*>(&sbn[1][c4]);
+        const f32x4 bmu = *reinterpret_cast<const f32x4*>(&sbn[2][c4]), bis = *reinterpret_cast<const f32x4*>(&sbn[3][c4]);
+        const f32x4 bk0 = *reinterpret_cast<const f32x4*>(&sbn[4][c4]), bk1 = *reinterpret_cast<const f32x4*>(&sbn[5][c4]);
+#pragma unroll
+        for (int j = 0; j < NDY; ++j) {
+          const int idx = tid + 256 * j;
+          const int p = idx / CPP, ch = idx % CPP;
+          const int gran = ch >> 2, sw = (p >> 1) & 1;
+          const int pg = (CT == 2) ? (gran ^ sw) : gran;
+          const f32x2 graw = {dreg[j][2 * hf], dreg[j][2 * hf + 1]}, yraw = {yreg[j][2 * hf], yreg[j][2 * hf + 1]};
+          const bf16x4 gv4 = __builtin_bit_cast(bf16x4, graw), yv4 = __builtin_bit_cast(bf16x4, yraw);
+          bf16x4 o4;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float yv = (float)yv4[i], gv = (float)gv4[i];
+            const float pre = fmaf(yv, bsc[i], bsh[i]);
+            const float dz = pre > 0.f ? gv : 0.f;
+            const float xh = (yv - bmu[i]) * bis[i];
+            o4[i] = (bf16_t)(bsc[i] * (dz - bk0[i] - xh * bk1[i]));
+          }
+          const bf16x4 z4 = {(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
+          *reinterpret_cast<bf16x4*>(sdy + p * RB + pg * 64 + (ch & 3) * 16 + 8 * hf) = (dmask >> j & 1u) ? o4 : z4;
+        }
+      }
     }
     __syncthreads();
     {   // the next tile streams in while this one is multiplied (unconditionally: the last tile fetches itself again)
@@ -325,6 +387,17 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const CfArgs a) {
     const int co = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), kk = l & 31;
     if (co < a.Cout) a.slab[((size_t)blockIdx.x * a.Cout + co) * 32 + kk] = s;
   }
+}
+
+template <int CT>
+__global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const CfArgs a) {
+  conv_first_wgrad_body<CT, false>(a);
+}
+// three workgroups per CU as the plain kernel (the grid is sized for it: all resident, one round), which the extra prefetch
+// registers and the BatchNorm constants only fit when the compiler is told so
+template <int CT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void conv_first_wgrad_bn_kernel(const CfArgs a) {
+  conv_first_wgrad_body<CT, true>(a);
 }
 
 // dw[co][k < K] = sum over workgroups of slab[wg][co][k] in a fixed order: thread (o, zg) of a block sums the slabs zg, zg + 16,
@@ -420,6 +493,39 @@ static int first_wgrad_grid(int ntiles) {
 extern "C" long long uz_conv3x3_first_wgrad_workspace_bytes(int N, int H, int W, int Cout) {
   const int ntiles = N * ((H + TH - 1) / TH) * ((W + TW - 1) / TW);
   return (long long)first_wgrad_grid(ntiles) * Cout * 32 * (long long)sizeof(float);
+}
+
+extern "C" int uz_conv3x3_first_wgrad_bn(int dtype, const float* x, int N, int C, int H, int W, const void* g, int ldg,
+                                         const void* y, int ldy, const float* scale, const float* shift, const float* mean,
+                                         const float* invstd, const double* sums, double count, int Cout, float* dw,
+                                         void* workspace, void* stream) {
+  int rc = check(dtype, N, C, H, W, Cout, ldg, "uz_conv3x3_first_wgrad_bn");
+  if (rc == UZ_OK) rc = check(dtype, N, C, H, W, Cout, ldy, "uz_conv3x3_first_wgrad_bn");
+  if (rc != UZ_OK) return rc;
+  UZ_REQUIRE(x && g && y && dw && workspace && ((uintptr_t)g & 15) == 0 && ((uintptr_t)y & 15) == 0,
+             "uz_conv3x3_first_wgrad_bn: null / unaligned pointer");
+  UZ_REQUIRE(scale && shift && mean && invstd && sums && count > 0, "uz_conv3x3_first_wgrad_bn: BatchNorm vectors / count");
+  CfArgs a = {};
+  a.x = x;
+  a.dy = g;
+  a.yraw = y;
+  a.ldyr = ldy;
+  a.bn_scale = scale;
+  a.bn_shift = shift;
+  a.bn_mean = mean;
+  a.bn_invstd = invstd;
+  a.bn_sums = sums;
+  a.inv_count = 1.0 / count;
+  a.slab = static_cast<float*>(workspace);
+  fill(a, N, C, H, W, Cout, ldg);
+  const int grid = first_wgrad_grid(a.ntiles);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (Cout == 64) hipLaunchKernelGGL(conv_first_wgrad_bn_kernel<2>, dim3(grid), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(conv_first_wgrad_bn_kernel<1>, dim3(grid), dim3(256), 0, s, a);
+  UZ_LAUNCH_CHECK("uz_conv3x3_first_wgrad_bn");
+  hipLaunchKernelGGL(conv_first_wgrad_reduce_kernel, dim3(Cout * 32 / 16), dim3(256), 0, s, a.slab, grid, Cout, C * 9, dw);
+  UZ_LAUNCH_CHECK("uz_conv3x3_first_wgrad_bn(reduce)");
+  return UZ_OK;
 }
 
 extern "C" int uz_conv3x3_first_wgrad(int dtype, const float* x, int N, int C, int H, int W, const void* dy, int lddy,

@@ -603,6 +603,96 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_kernel(const BnBwdArgs a) {
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// The apply pass (PASS 2: no pool, ReLU, bf16) of the block in front of the 1x1 head, with a gradient that is not a tensor
+// (uz_bn_relu_bwd_apply_head): the head's input gradient dx[p][c] = sum_k g[n][k][hw] w[k][c] has rank K <= 8 and this pass
+// is its only reader, so it is formed here from the K logit gradients of the pixel (4 K bytes, against 2 C bytes of a stored
+// dx) exactly as outconv_bwd_kernel would have stored it: the fmaf chain over ascending k, rounded to bf16 and widened
+// again.  From there on the expressions are those of bn_relu_bwd_kernel<bf16_t, false, 2>, on the same grid and walk.
+// ------------------------------------------------------------------------------------------
+struct BnBwdHeadArgs {
+  const bf16_t* y;
+  bf16_t* dy;
+  const float* scale;
+  const float* shift;
+  const float* mean;
+  const float* invstd;
+  const double* sums;   // [2][C] totals
+  const float* g;       // logit gradients, fp32 NKHW
+  const float* w;       // head weights [K][C]
+  double inv_count;
+  int P, HW, C, ldy, lddy, rev;
+};
+
+template <int KOUT>
+__global__ __launch_bounds__(256) void bn_relu_bwd_head_kernel(const BnBwdHeadArgs a) {
+  typedef bf16_t T;
+  constexpr int VEC = ElemTraits<T>::VEC, NPIX = 4;
+  const T* __restrict__ y = a.y;
+  const float* __restrict__ g = a.g;
+  T* __restrict__ dy = a.dy;
+  const int CC = a.C / VEC;
+  const int cc = blockIdx.y * blockDim.x + threadIdx.x;  // channel chunk of this thread
+  const bool cok = cc < CC;
+  const int c0 = (cok ? cc : 0) * VEC;
+  const long long units = a.P;   // < 2^31 (checked on the host)
+
+  float sc[VEC], sh[VEC], mu[VEC], is[VEC], k0[VEC], k1[VEC], wr[KOUT][VEC];
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) {
+    sc[i] = a.scale[c0 + i];
+    sh[i] = a.shift[c0 + i];
+    mu[i] = a.mean[c0 + i];
+    is[i] = a.invstd[c0 + i];
+    k0[i] = (float)(a.sums[c0 + i] * a.inv_count);
+    k1[i] = (float)(a.sums[a.C + c0 + i] * a.inv_count);
+#pragma unroll
+    for (int k = 0; k < KOUT; ++k) wr[k][i] = a.w[k * a.C + c0 + i];
+  }
+  const long long ustride = (long long)gridDim.x * blockDim.y;
+  const bool rev = a.rev != 0;
+  for (long long u0 = (long long)blockIdx.x * blockDim.y + threadIdx.y; u0 < units && cok; u0 += NPIX * ustride) {
+    size_t pix[NPIX];   // pixel of slot k; a slot past the end reads the last pixel and stores nothing
+    bool in[NPIX];
+#pragma unroll
+    for (int k = 0; k < NPIX; ++k) {
+      const long long q = u0 + k * ustride;
+      in[k] = q < units;
+      pix[k] = (size_t)(in[k] ? (rev ? units - 1 - q : q) : units - 1);
+    }
+    // every load of the iteration, logit gradients included, is issued unconditionally before the first use
+    Vec16<T> yr[NPIX];
+    float gq[NPIX][KOUT];
+#pragma unroll
+    for (int k = 0; k < NPIX; ++k) {
+      yr[k] = ld16(y + pix[k] * a.ldy + c0);
+      const int p = (int)pix[k];
+      const int img = (KOUT == 1) ? 0 : p / a.HW;   // KOUT == 1: NCHW index == pixel index
+      const int hw = p - img * a.HW;
+#pragma unroll
+      for (int kk = 0; kk < KOUT; ++kk) gq[k][kk] = g[((size_t)img * KOUT + kk) * a.HW + hw];
+    }
+#pragma unroll
+    for (int k = 0; k < NPIX; ++k) {
+      if (!in[k]) continue;
+      float out[VEC];
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) {
+        float d = 0.f;
+#pragma unroll
+        for (int kk = 0; kk < KOUT; ++kk) d = fmaf(gq[k][kk], wr[kk][i], d);
+        const float gv = (float)(T)d;   // the gradient as outconv_bwd_kernel stores it
+        const float yv = (float)yr[k].v[i];
+        const float pre = fmaf(yv, sc[i], sh[i]);
+        const float dz = pre > 0.f ? gv : 0.f;
+        const float xh = (yv - mu[i]) * is[i];
+        out[i] = sc[i] * (dz - k0[i] - xh * k1[i]);
+      }
+      store_f(dy + pix[k] * a.lddy + c0, out);
+    }
+  }
+}
+
 // totals[2][C] (double) = sum over the partial rows; dbeta = totals[0], dgamma = totals[1]
 template <int EW>
 __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __restrict__ part, int rows,
@@ -1638,6 +1728,46 @@ extern "C" int uz_bn_relu_bwd_apply_fin(const uz_bnbwd_desc* d, const void* y, c
                              : bnbwd_launch<float, 2, true>(d, a, gpool != nullptr, s);
 }
 
+extern "C" int uz_bn_relu_bwd_apply_head_supported(int dtype, int C, int Kout) {
+  return dtype == UZ_BF16 && C > 0 && C % 8 == 0 && Kout >= 1 && Kout <= OUTCONV_MAXK;
+}
+
+extern "C" int uz_bn_relu_bwd_apply_head(const uz_bnbwd_desc* d, const void* y, const float* scale, const float* shift,
+                                         const float* mean, const float* invstd, const float* g_nchw, const float* w,
+                                         int Kout, const double* sums, double count, void* dy, void* stream) {
+  UZ_REQUIRE(d != nullptr, "uz_bn_relu_bwd_apply_head: null descriptor");
+  UZ_REQUIRE(uz_bn_relu_bwd_apply_head_supported(d->dtype, d->C, Kout), "uz_bn_relu_bwd_apply_head: dtype=%d C=%d Kout=%d unsupported",
+             d->dtype, d->C, Kout);
+  UZ_REQUIRE(y && scale && shift && mean && invstd && g_nchw && w && sums && dy, "uz_bn_relu_bwd_apply_head: null pointer");
+  UZ_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && (long long)d->N * d->H * d->W < (1LL << 31), "uz_bn_relu_bwd_apply_head: bad shape");
+  UZ_REQUIRE(d->ldy % 8 == 0 && d->ldy >= d->C && d->lddy % 8 == 0 && d->lddy >= d->C, "uz_bn_relu_bwd_apply_head: bad ldy / lddy");
+  UZ_REQUIRE((d->pool_ceil & 3) == 0, "uz_bn_relu_bwd_apply_head: a ReLU block without a pool only");
+  UZ_REQUIRE(count > 0, "uz_bn_relu_bwd_apply_head: count");
+  BnBwdHeadArgs a;
+  a.y = static_cast<const bf16_t*>(y);
+  a.dy = static_cast<bf16_t*>(dy);
+  a.scale = scale;
+  a.shift = shift;
+  a.mean = mean;
+  a.invstd = invstd;
+  a.sums = sums;
+  a.g = g_nchw;
+  a.w = w;
+  a.inv_count = 1.0 / count;
+  a.P = d->N * d->H * d->W;
+  a.HW = d->H * d->W;
+  a.C = d->C;
+  a.ldy = d->ldy;
+  a.lddy = d->lddy;
+  a.rev = (d->pool_ceil & 4) != 0;
+  dim3 grid, block;
+  bnbwd_shape(d, false, &grid, &block, 2);   // the grid and the walk of uz_bn_relu_bwd_apply
+  hipStream_t s = (hipStream_t)stream;
+  UZ_KOUT_SWITCH(Kout, hipLaunchKernelGGL((bn_relu_bwd_head_kernel<KOUT>), grid, block, 0, s, a))
+  UZ_LAUNCH_CHECK("uz_bn_relu_bwd_apply_head");
+  return UZ_OK;
+}
+
 extern "C" int uz_outconv_fwd(int dtype, const void* x, int ldx, int N, int HW, int C, const float* w,
                               const float* b, int Kout, float* out_nchw, void* stream) {
   UZ_REQUIRE(dtype == UZ_F32 || dtype == UZ_BF16, "uz_outconv_fwd: bad dtype");
@@ -1704,11 +1834,13 @@ extern "C" int uz_outconv_bwd_bnred(int dtype, const void* x, int ldx, int N, in
                                     void* stream) {
   UZ_REQUIRE(dtype == UZ_BF16, "uz_outconv_bwd_bnred: bf16 only");
   // x == NULL: the activation was never written down (uz_outconv_fwd_xf); the kernel forms it from bn_y
-  UZ_REQUIRE(w && g_nchw && dw && db && workspace && dx && bn_y && scale && shift && mean && invstd && bn_partial,
+  // dx == NULL: nothing is stored -- the reader forms the gradient itself (uz_bn_relu_bwd_apply_head); the sums stay those of
+  // "the gradient as stored"
+  UZ_REQUIRE(w && g_nchw && dw && db && workspace && bn_y && scale && shift && mean && invstd && bn_partial,
              "uz_outconv_bwd_bnred: null pointer");
   UZ_REQUIRE(Kout >= 1 && Kout <= OUTCONV_MAXK, "uz_outconv_bwd_bnred: Kout=%d", Kout);
   UZ_REQUIRE(C % 8 == 0 && C / 8 <= 64, "uz_outconv_bwd_bnred: C=%d unsupported", C);
-  UZ_REQUIRE((x == nullptr || (ldx % 8 == 0 && ldx >= C)) && lddx % 8 == 0 && lddx >= C && ld_bny % 8 == 0 && ld_bny >= C && N > 0 &&
+  UZ_REQUIRE((x == nullptr || (ldx % 8 == 0 && ldx >= C)) && (dx == nullptr || (lddx % 8 == 0 && lddx >= C)) && ld_bny % 8 == 0 && ld_bny >= C && N > 0 &&
                  HW > 0 && (long long)N * HW < (1LL << 31), "uz_outconv_bwd_bnred: bad shape");
   const int g = outconv_bwd_grid(dtype, N, HW, C);
   float* part = static_cast<float*>(workspace);

@@ -150,6 +150,15 @@ class Engine:
     # through the map (uz_outconv_fwd_xf), its backward needs the raw tensor only (uz_outconv_bwd_bnred with x = NULL) --
     # one full-resolution apply pass and one full-resolution read fewer per step
     fold_bn_apply_head = True
+    # ... and that head's input gradient, a rank-K tensor (K logit gradients per pixel times the K x C weights) with one reader,
+    # is not written down either: uz_outconv_bwd_bnred leaves only the weight / bias gradients and the BatchNorm partial rows,
+    # and the apply pass of the producing block forms the gradient itself (uz_bn_relu_bwd_apply_head) -- one full-resolution
+    # write and one read fewer per step (class-level: tools/ab_step.py times both ways)
+    fold_head_grad = True
+    # the BatchNorm + ReLU backward of the FIRST layer (direct_first_conv) has one reader, the weight gradient (the image needs
+    # no input gradient): that kernel reads the activation's gradient through the backward map
+    # (uz_conv3x3_first_wgrad_bn) and the apply pass with its dy tensor does not run (class-level, as above)
+    fold_first_bn_bwd = True
     # the BatchNorm finalize launches (forward: statistics -> scale / shift; backward: partial rows -> totals) riding in the
     # launch of the element pass that consumes them (uz_bn_relu_add_apply_fin, uz_bn_relu_bwd_apply_fin; 36 launches of
     # ~5 us per unet step, 448 per u2net step).  OFF: measured slower (round 5, tools/ab_step.py, same box: unet 6.654 vs
@@ -459,6 +468,8 @@ class Engine:
                 g1 = gs[1] if len(gs) > 1 else None
                 if g0 is None and gp is None:
                     return  # nothing downstream used this activation
+                head = isinstance(g0, ops.HeadGrad)   # the 1x1 head wrote no gradient (fold_head_grad): the apply pass forms it
+                assert not head or (g1 is None and gp is None and residual is None and relu and not frozen and pooled is None)
                 if residual is not None:
                     # the residual branch needs the TOTAL gradient of act as one tensor; the pool's
                     # argmax is over act (= relu + residual), not over relu(bn(y))
@@ -468,17 +479,26 @@ class Engine:
                         g0, g1, gp = tot, None, None
                     if residual.needs_grad:
                         residual.add_grad(g0)
-                dy = self.new_act(N, H, W, Cout)
+                # the first layer: the weight gradient is dy's only reader and forms it itself (uz_conv3x3_first_wgrad_bn); only
+                # the reduction and its finalize (dgamma, dbeta, the totals) run here and no dy exists
+                fold_first = (self.fold_first_bn_bwd and image is not None and not frozen and relu and not head
+                              and self.dtype == torch.bfloat16 and pooled is None and residual is None and g1 is None
+                              and gp is None and not self.fuse_bn_finalize)
+                dy = None if fold_first else self.new_act(N, H, W, Cout)
                 dgamma, dbeta = self._dst(bn.weight), self._dst(bn.bias)
                 if dgamma is None:
                     dgamma = torch.empty(Cout, dtype=torch.float32, device=self.device)
                 if dbeta is None:
                     dbeta = torch.empty(Cout, dtype=torch.float32, device=self.device)
-                # g0 came from a sole reader's input-gradient kernel with the reduction already done in its epilogue
-                parts = getattr(g0, "bn_partials", None) if (g1 is None and gp is None and residual is None) else None
-                ops.bn_relu_bwd(y, vec, g0, g1, gp, self._bn_sums(Cout), dy, dgamma, dbeta, pool_ceil, relu=relu,
-                                partials=parts, frozen=frozen, fin_flag=None if frozen else self._fin_flag(),
-                                reverse=self.reverse_element_passes)
+                sums = self._bn_sums(Cout)
+                if head:
+                    ops.bn_relu_bwd_head(y, vec, g0, sums, dy, dgamma, dbeta, reverse=self.reverse_element_passes)
+                else:
+                    # g0 came from a sole reader's input-gradient kernel with the reduction already done in its epilogue
+                    parts = getattr(g0, "bn_partials", None) if (g1 is None and gp is None and residual is None) else None
+                    ops.bn_relu_bwd(y, vec, g0, g1, gp, sums, dy, dgamma, dbeta, pool_ceil, relu=relu,
+                                    partials=parts, frozen=frozen, fin_flag=None if frozen else self._fin_flag(),
+                                    reverse=self.reverse_element_passes)
                 self._give_grad(bn.weight, dgamma)
                 self._give_grad(bn.bias, dbeta)
                 if conv.bias is not None:
@@ -492,7 +512,10 @@ class Engine:
                     if image._version != image_version:
                         raise RuntimeError("the network input was modified in place between forward and backward: the first "
                                            "convolution's weight gradient reads it (pass a copy, or finish backward first)")
-                    self._give_grad(conv.weight, ops.conv_first_wgrad(image, dy, out=self._dst(conv.weight)))
+                    if fold_first:
+                        self._give_grad(conv.weight, ops.conv_first_wgrad_bn(image, g0, y, vec, sums, out=self._dst(conv.weight)))
+                    else:
+                        self._give_grad(conv.weight, ops.conv_first_wgrad(image, dy, out=self._dst(conv.weight)))
                 elif im2col:
                     dwp = ops.wgrad(dy, x, (Cout, x.C), ntaps=1)
                     cin = conv.in_channels
@@ -1978,16 +2001,28 @@ class Engine:
         logits = ops.outconv_fwd(x, w, b, xform=xf)
         if self.record:
             def bwd(g_logits: torch.Tensor):
-                dx = self.new_act(x.N, x.H, x.W, x.C) if (x.needs_grad or xf is not None) else None
                 dwt = self._dst(conv.weight)
                 dbt = self._dst(conv.bias) if conv.bias is not None else None
                 src = getattr(x, "bn_src", None) if (sole_reader and (self.fuse_bn_reduce_convt or xf is not None)) else None
-                dw, db = ops.outconv_bwd(x, w, g_logits.contiguous().float(), dx,
-                                         dwt.view(K, x.C) if dwt is not None else None, dbt, bnred=src, lazy=xf is not None)
+                gl = g_logits.contiguous().float()
+                # lazy head, sole reader: the rank-K gradient is not written down; the producing block's apply pass forms it
+                # from a virtual gradient (logit gradients, weights, the BatchNorm partial rows) -- where that pass takes the
+                # shape and its finalize is a launch of its own
+                virt = (xf is not None and self.fold_head_grad and src is not None and self.training
+                        and not self.fuse_bn_finalize and ops.bn_bwd_head_supported(src[0], K))
+                dx = self.new_act(x.N, x.H, x.W, x.C) if ((x.needs_grad or xf is not None) and not virt) else None
+                if virt:
+                    dw, db, part = ops.outconv_bwd(x, w, gl, None, dwt.view(K, x.C) if dwt is not None else None, dbt,
+                                                   bnred=src, lazy=True, store_dx=False)
+                else:
+                    dw, db = ops.outconv_bwd(x, w, gl, dx, dwt.view(K, x.C) if dwt is not None else None, dbt, bnred=src,
+                                             lazy=xf is not None)
                 self._give_grad(conv.weight, dwt if dwt is not None else dw.reshape(conv.weight.shape))
                 if conv.bias is not None:
                     self._give_grad(conv.bias, db)
-                if dx is not None:
+                if virt:
+                    x.add_grad(ops.HeadGrad(gl, w, part))
+                elif dx is not None:
                     x.add_grad(dx)
 
             self._heads.append((bwd, 1))

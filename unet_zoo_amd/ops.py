@@ -285,6 +285,30 @@ def conv_first_wgrad(x: torch.Tensor, dy: Act, out: Optional[torch.Tensor] = Non
     return out
 
 
+def conv_first_wgrad_bn(x: torch.Tensor, g: Act, y: Act, vec: torch.Tensor, sums: torch.Tensor,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv_first_wgrad(x, dy) with dy = the BatchNorm + ReLU backward of the layer formed inside the kernel from the gradient
+    g of the activation, the raw convolution output y, vec = (scale, shift, mean, invstd) and the float64 (2, C) totals of
+    uz_bn_bwd_finalize (uz_conv3x3_first_wgrad_bn): that dy is never written down; the same bits as the two launches"""
+    L.require_cuda(x, g.buf, y.buf)
+    N, C, H, W = x.shape
+    Cout = g.C
+    assert (y.N, y.H, y.W, y.C) == (g.N, g.H, g.W, g.C) == (N, H, W, Cout) and g.dtype == y.dtype == torch.bfloat16
+    assert sums.dtype == torch.float64 and sums.shape == (2, Cout) and sums.is_contiguous()
+    lib = L.load()
+    ws_bytes = L.check_count(lib.uz_conv3x3_first_wgrad_workspace_bytes(N, H, W, Cout), "uz_conv3x3_first_wgrad_workspace_bytes")
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((Cout, C, 3, 3), dtype=torch.float32, device=x.device)
+    assert out.numel() == Cout * C * 9 and out.is_contiguous() and out.dtype == torch.float32
+    with _Timed("wgrad_first_bf16", 2.0 * N * H * W * 9 * C * Cout, 4.0 * x.numel() + 4.0 * g.P * Cout):
+        L.check(lib.uz_conv3x3_first_wgrad_bn(L.dtype_code(g.dtype), x.data_ptr(), N, C, H, W, g.ptr(), g.ld, y.ptr(), y.ld,
+                                              vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(), vec[3].data_ptr(),
+                                              sums.data_ptr(), float(y.P), Cout, out.data_ptr(), ws.data_ptr(), L.stream_ptr()),
+                "uz_conv3x3_first_wgrad_bn")
+    return out
+
+
 def conv_kernel_name(d, with_workspace: bool = False) -> str:
     """uz_conv_igemm_kernel_name(): the kernel family the library's plan picks for a ConvDesc (labels of the per-kernel
     timing of bench.py; tests use it to assert which generation they exercise)"""
@@ -566,7 +590,7 @@ BN_BWD_ALTERNATE = True
 
 
 def bn_relu_bwd(y: Act, vec: torch.Tensor, g0: Optional[Act], g1: Optional[Act],
-                gpool: Optional[Act], sums: torch.Tensor, dy: Act, dgamma: torch.Tensor,
+                gpool: Optional[Act], sums: torch.Tensor, dy: Optional[Act], dgamma: torch.Tensor,
                 dbeta: torch.Tensor, pool_ceil: bool = False, relu: bool = True,
                 partials: Optional[torch.Tensor] = None, frozen: bool = False,
                 fin_flag: Optional[torch.Tensor] = None, reverse: bool = False) -> None:
@@ -576,12 +600,15 @@ def bn_relu_bwd(y: Act, vec: torch.Tensor, g0: Optional[Act], g1: Optional[Act],
     frozen: the forward used RUNNING statistics (model.eval(); fine-tuning with frozen BatchNorm, which the reference
     allows): vec holds (scale, shift, running_mean, 1/sqrt(running_var + eps)); mean and variance are constants, so
     dy = scale * g * mask without the two batch-correction terms -- the same kernels with the sums zeroed between the
-    passes; dgamma = sum g*mask*xhat and dbeta = sum g*mask are the first pass's results as they are."""
+    passes; dgamma = sum g*mask*xhat and dbeta = sum g*mask are the first pass's results as they are.
+    dy = None: the first pass and its finalize only (sums, dgamma, dbeta); the caller's next kernel forms dy itself
+    (conv_first_wgrad_bn)."""
     lib = L.load()
+    assert dy is not None or (fin_flag is None and not frozen)
     def desc(rev):
         return L.BnBwdDesc(L.dtype_code(y.dtype), y.N, y.H, y.W, y.C, y.ld,
                            g0.ld if g0 is not None else 0, g1.ld if g1 is not None else 0,
-                           gpool.ld if gpool is not None else 0, dy.ld,
+                           gpool.ld if gpool is not None else 0, dy.ld if dy is not None else 0,
                            int(pool_ceil) | (0 if relu else 2) | (4 if rev else 0))   # bit 2: walk from the end (see bn_relu_apply)
     d = desc(reverse)
     # the apply pass after a reduce pass of its own starts where that pass ENDED (the opposite walk): what the reduce pass read
@@ -622,11 +649,49 @@ def bn_relu_bwd(y: Act, vec: torch.Tensor, g0: Optional[Act], g1: Optional[Act],
         with _Timed("bn_relu_bwd_reduce", 0.0, es * y.P * y.C * (1 + nsrc)):
             L.check(lib.uz_bn_relu_bwd_reduce(byref(d), *args, ws.data_ptr(), sums.data_ptr(),
                                               dgamma.data_ptr(), dbeta.data_ptr(), s), "uz_bn_relu_bwd_reduce")
+    if dy is None:
+        return
     if frozen:
         sums.zero_()
     with _Timed("bn_relu_bwd_apply", 0.0, es * y.P * y.C * (2 + nsrc)):
         L.check(lib.uz_bn_relu_bwd_apply(byref(d_apply), *args, sums.data_ptr(), float(y.P), dy.ptr(), s),
                 "uz_bn_relu_bwd_apply")
+
+
+class HeadGrad:
+    """The gradient of the activation in front of the 1x1 head that nobody wrote down (Engine.fold_head_grad): its only reader,
+    the BatchNorm backward of the producing block, forms it from the logit gradients g (N, K, H, W) fp32 and the head's
+    weights w (K, C) (bn_relu_bwd_head); bn_partials: the rows of that BatchNorm's first backward pass, which
+    uz_outconv_bwd_bnred took from the gradient as it WOULD have been stored"""
+    __slots__ = ("g", "w", "bn_partials")
+
+    def __init__(self, g: torch.Tensor, w: torch.Tensor, bn_partials: torch.Tensor):
+        self.g, self.w, self.bn_partials = g, w, bn_partials
+
+
+def bn_bwd_head_supported(y: Act, K: int) -> bool:
+    return bool(L.load().uz_bn_relu_bwd_apply_head_supported(L.dtype_code(y.dtype), y.C, K)) and y.ld % 8 == 0
+
+
+def bn_relu_bwd_head(y: Act, vec: torch.Tensor, hg: HeadGrad, sums: torch.Tensor, dy: Act, dgamma: torch.Tensor,
+                     dbeta: torch.Tensor, reverse: bool = False) -> None:
+    """bn_relu_bwd(y, vec, g0 = the head's input gradient, partials = hg.bn_partials) without that tensor: the finalize of
+    the rows, then the apply pass that forms the gradient itself (uz_bn_relu_bwd_apply_head); training, ReLU, no pool"""
+    lib = L.load()
+    K = hg.w.shape[0]
+    parts = hg.bn_partials
+    assert hg.g.dtype == torch.float32 and hg.g.is_contiguous() and hg.g.shape == (y.N, K, y.H, y.W)
+    assert hg.w.dtype == torch.float32 and hg.w.is_contiguous() and hg.w.shape == (K, y.C)
+    assert parts.shape[1:] == (2, y.C) and parts.is_contiguous() and bn_bwd_head_supported(y, K)
+    s = L.stream_ptr()
+    L.check(lib.uz_bn_bwd_finalize(parts.data_ptr(), parts.shape[0], y.C, sums.data_ptr(), dgamma.data_ptr(),
+                                   dbeta.data_ptr(), s), "uz_bn_bwd_finalize")
+    d = L.BnBwdDesc(L.dtype_code(y.dtype), y.N, y.H, y.W, y.C, y.ld, 0, 0, 0, dy.ld, 4 if reverse else 0)
+    es = y.buf.element_size()
+    with _Timed("bn_relu_bwd_apply_head", 2.0 * K * y.P * y.C, es * y.P * y.C * 2 + 4.0 * K * y.P):
+        L.check(lib.uz_bn_relu_bwd_apply_head(byref(d), y.ptr(), vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(),
+                                              vec[3].data_ptr(), hg.g.data_ptr(), hg.w.data_ptr(), K, sums.data_ptr(),
+                                              float(y.P), dy.ptr(), s), "uz_bn_relu_bwd_apply_head")
 
 
 def outconv_xform_supported(x: Act, K: int) -> bool:
@@ -653,11 +718,12 @@ def outconv_fwd(x: Act, w: torch.Tensor, b: torch.Tensor, xform: Optional[tuple]
 
 def outconv_bwd(x: Act, w: torch.Tensor, g: torch.Tensor, dx: Optional[Act],
                 dw: Optional[torch.Tensor] = None, db: Optional[torch.Tensor] = None,
-                bnred: Optional[tuple] = None, lazy: bool = False):
+                bnred: Optional[tuple] = None, lazy: bool = False, store_dx: bool = True):
     """bnred = (bn_y, vec): x = relu(bn(bn_y)) is read by this head only; the BatchNorm-backward sums of dx are taken in
     the same pass (uz_outconv_bwd_bnred) and their partial rows left in dx.bn_partials (bf16 only; else ignored).
     lazy: x was never written down (outconv_fwd(xform=...)): x is only a shape here, the kernel forms the activation from
-    bn_y (bnred and dx are then required)"""
+    bn_y (bnred is then required).  store_dx=False (with lazy): dx is not written either -- its reader forms it
+    (bn_relu_bwd_head) -- and the partial rows are returned as a third value"""
     lib = L.load()
     K = w.shape[0]
     assert g.dtype == torch.float32 and g.is_contiguous() and g.shape == (x.N, K, x.H, x.W)
@@ -671,16 +737,20 @@ def outconv_bwd(x: Act, w: torch.Tensor, g: torch.Tensor, dx: Optional[Act],
                         "uz_outconv_bwd_workspace_bytes")
     ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev)
     if lazy:
-        assert bnred is not None and dx is not None and x.dtype == torch.bfloat16 and (bnred[0].P, bnred[0].C) == (x.P, x.C), \
+        assert bnred is not None and (dx is not None) == store_dx and x.dtype == torch.bfloat16 and (bnred[0].P, bnred[0].C) == (x.P, x.C), \
             "a head on a lazy activation takes its backward through uz_outconv_bwd_bnred"
-    if bnred is not None and dx is not None and x.dtype == torch.bfloat16 and (bnred[0].P, bnred[0].C) == (x.P, x.C):
+    assert store_dx or lazy
+    if bnred is not None and (dx is not None or not store_dx) and x.dtype == torch.bfloat16 and (bnred[0].P, bnred[0].C) == (x.P, x.C):
         bn_y, vec4 = bnred
         rows = L.check_count(lib.uz_outconv_bwd_rows(code, x.N, x.H * x.W, x.C), "uz_outconv_bwd_rows")
         part = torch.empty((rows, 2, x.C), dtype=torch.float32, device=dev)
         L.check(lib.uz_outconv_bwd_bnred(code, None if lazy else x.ptr(), x.ld, x.N, x.H * x.W, x.C, w.data_ptr(), K, g.data_ptr(),
-                                         dx.ptr(), dx.ld, dw.data_ptr(), db.data_ptr(), ws.data_ptr(), bn_y.ptr(), bn_y.ld,
+                                         dx.ptr() if store_dx else None, dx.ld if store_dx else 0, dw.data_ptr(), db.data_ptr(),
+                                         ws.data_ptr(), bn_y.ptr(), bn_y.ld,
                                          vec4[0].data_ptr(), vec4[1].data_ptr(), vec4[2].data_ptr(), vec4[3].data_ptr(),
                                          part.data_ptr(), L.stream_ptr()), "uz_outconv_bwd_bnred")
+        if not store_dx:
+            return dw.view(K, x.C), db, part
         dx.bn_partials = part
         return dw.view(K, x.C), db
     L.check(lib.uz_outconv_bwd(code, x.ptr(), x.ld, x.N, x.H * x.W, x.C, w.data_ptr(), K, g.data_ptr(),
