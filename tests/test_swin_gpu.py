@@ -198,19 +198,21 @@ def _attention_core_ref(qkv, tau, bias, heads, ws, shift):
                                                      (1, 14, 14, 6, 7, 3, 49), (2, 8, 8, 12, 4, 2, 16),
                                                      (3, 2, 2, 24, 2, 0, 49), (1, 8, 16, 3, 4, 2, 64)])
 def test_window_attention_core_forward_backward(dt, B, H, W, heads, ws, shift, Nt):
+    """at most 8 windows: one window per workgroup (tests/test_winattn_walk_gpu.py holds the walk over several); the reference
+    is float64 on the dtype-rounded operands, as there"""
     g = torch.Generator().manual_seed(45)
     C, N = heads * 32, ws * ws
-    qkv = rnd(dt, torch.randn(B, H, W, 3 * C, generator=g)).requires_grad_(True)
+    qkv = rnd(dt, torch.randn(B, H, W, 3 * C, generator=g)).double().requires_grad_(True)
     tau = (torch.rand(heads, Nt, Nt, generator=g) * 1.5 + 0.005)
     tau[:, 0, 1] = 0.002                                      # below the 0.01 clip: zero tau gradient there
-    tau.requires_grad_(True)
-    bias = (torch.randn(heads, N, N, generator=g) * 0.5).requires_grad_(True)
+    tau = tau.double().requires_grad_(True)
+    bias = (torch.randn(heads, N, N, generator=g) * 0.5).double().requires_grad_(True)
     dout = rnd(dt, torch.randn(B, H, W, C, generator=g))
     ref = _attention_core_ref(qkv, tau, bias, heads, ws, shift)
-    ref.backward(dout)
+    ref.backward(dout.double())
     qa = tokens_to_act(qkv.detach(), dt)
     out = ops.new_act(B, H, W, C, dt, DEV)
-    td, bd = tau.detach().to(DEV).contiguous(), bias.detach().to(DEV).contiguous()
+    td, bd = tau.detach().float().to(DEV).contiguous(), bias.detach().float().to(DEV).contiguous()
     lse = ops.winattn_fwd(qa, td, bd, out, heads, ws, shift)
     tol = 1e-5 if dt == torch.float32 else 1e-2
     assert relerr(act_to_tokens(out), ref.detach()) < tol
