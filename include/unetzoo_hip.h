@@ -171,6 +171,23 @@ int uz_conv_igemm_xf_supported(const uz_conv_desc* d);
 int uz_conv_igemm_xf(const uz_conv_desc* d, const void* x, const float* in_scale, const float* in_shift,
                      const void* w_packed, const float* bias, void* y, float* stats_partial, void* stream);
 
+/* Convolution with the eval-mode BatchNorm [+ ReLU] behind it formed in the epilogue: out_scale / out_shift are the constant
+ * vectors of uz_bn_eval_scale(), known before the launch.  Per output element, from the fp32 accumulator:
+ *   v = acc + bias[co];  a = fmaf(v, out_scale[co], out_shift[co]);  if (relu) a = max(a, 0);  y[p * ldy + co] = T(a)
+ * -- uz_bn_relu_apply's expression on the UNROUNDED fp32 value, rounded once to the run dtype (fp32: bit-identical to
+ * uz_conv_igemm + uz_bn_relu_apply; bf16: one rounding instead of two).  The raw convolution output is neither written nor
+ * read back and no statistics rows are written.  ldy may exceed Nout (one half of a concat buffer): only [0, Nout) of a
+ * pixel is touched.  Problems with UZ_STORE_PLAIN and UZ_TAPS_CONV / UZ_TAPS_CONV_UP2 that uz_conv_igemm plans on the direct
+ * 3x3 kernels with a workgroup- or wave-wide staged epilogue (conv3x3_pp*, conv3x3_direct_*, both dtypes) or on the generic
+ * kernel (igemm_*), without a split plan (uz_conv_igemm_bnact_supported() == 1); the split-K / tap-split plans, the
+ * weights-in-registers kernel (conv3x3_res64_*), the LDS-DMA GEMM, the gather modes and the shuffle store: UZ_ENOTIMPL, no
+ * launch -- the caller then runs uz_conv_igemm + uz_bn_relu_apply.  The refusal follows the PLAN of the descriptor, not how
+ * the call is made: a problem that uz_conv_igemm_ws would split over a workspace is refused although the unsplit form of
+ * the same kernel exists (it is the slower route for those shapes).  out_scale / out_shift: 16-byte aligned. */
+int uz_conv_igemm_bnact_supported(const uz_conv_desc* d);
+int uz_conv_igemm_bnact(const uz_conv_desc* d, const void* x, const void* w_packed, const float* bias,
+                        const float* out_scale, const float* out_shift, int relu, void* y, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Weight gradient (reduction over pixels), fp32 output in the reference's parameter layout.
  *   out[i, j, tap] (+)= sum_p L[p, i] * R[pix(p, tap), j]
@@ -254,6 +271,11 @@ int uz_conv3x3_first_supported(int dtype, int C, int Cout);
 int uz_conv3x3_first_rows(int N, int H, int W);
 int uz_conv3x3_first_fwd(int dtype, const float* x, int N, int C, int H, int W, const float* w, const float* bias, int Cout,
                          void* y, int ldy, float* stats, void* stream);
+/* uz_conv3x3_first_fwd with the eval-mode BatchNorm [+ ReLU] in the epilogue (the semantics of uz_conv_igemm_bnact); no
+ * statistics. */
+int uz_conv3x3_first_fwd_bnact(int dtype, const float* x, int N, int C, int H, int W, const float* w, const float* bias,
+                               int Cout, const float* out_scale, const float* out_shift, int relu, void* y, int ldy,
+                               void* stream);
 long long uz_conv3x3_first_wgrad_workspace_bytes(int N, int H, int W, int Cout);
 int uz_conv3x3_first_wgrad(int dtype, const float* x, int N, int C, int H, int W, const void* dy, int lddy, int Cout, float* dw,
                            void* workspace, void* stream);

@@ -53,6 +53,7 @@ EXPORTS = (
     "uz_softmax_workspace_bytes", "uz_add_map", "uz_dropout", "uz_chanscale_relu", "uz_chanattn_probs_fwd", "uz_chanattn_probs_bwd",
     "uz_conv5x5_grid_m", "uz_conv5x5", "uz_wgrad5x5_workspace_bytes", "uz_wgrad5x5",
     "uz_bn_elu_apply", "uz_bn_elu_bwd_rows", "uz_bn_elu_bwd_reduce", "uz_bn_elu_bwd_apply",
+    "uz_conv_igemm_bnact_supported", "uz_conv_igemm_bnact", "uz_conv3x3_first_fwd_bnact",
 )
 
 
@@ -177,6 +178,8 @@ def load():
     lib.uz_conv_igemm_bnred_supported.argtypes = [POINTER(ConvDesc)]
     lib.uz_conv_igemm_xf_supported.argtypes = [POINTER(ConvDesc)]
     lib.uz_conv_igemm_xf.argtypes = [POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.uz_conv_igemm_bnact_supported.argtypes = [POINTER(ConvDesc)]
+    lib.uz_conv_igemm_bnact.argtypes = [POINTER(ConvDesc), vp, vp, vp, vp, vp, c_int, vp, vp]
     lib.uz_conv_igemm_kernel_name.argtypes = [POINTER(ConvDesc), c_int, c_char_p, c_int]
     lib.uz_profile_arm.argtypes = [vp, vp]
     lib.uz_profile_disarm.argtypes = []
@@ -213,6 +216,7 @@ def load():
     lib.uz_conv3x3_first_supported.argtypes = [ip, ip, ip]
     lib.uz_conv3x3_first_rows.argtypes = [ip, ip, ip]
     lib.uz_conv3x3_first_fwd.argtypes = [ip, vp, ip, ip, ip, ip, vp, vp, ip, vp, ip, vp, vp]
+    lib.uz_conv3x3_first_fwd_bnact.argtypes = [ip, vp, ip, ip, ip, ip, vp, vp, ip, vp, vp, ip, vp, ip, vp]
     lib.uz_conv3x3_first_wgrad_workspace_bytes.argtypes = [ip, ip, ip, ip]
     lib.uz_conv3x3_first_wgrad_workspace_bytes.restype = ctypes.c_longlong
     lib.uz_conv3x3_first_wgrad.argtypes = [ip, vp, ip, ip, ip, ip, vp, ip, ip, vp, vp, vp]

@@ -44,6 +44,11 @@ struct DirectArgs {
   const float* bn_mean;
   const float* bn_invstd;
   int ld_bny;
+  // ACT (template parameter, uz_conv_igemm_bnact): the epilogue stores relu?(fma(acc + bias, act_scale[co], act_shift[co])) --
+  // the eval-mode BatchNorm [+ ReLU] of uz_bn_relu_apply on the fp32 result, rounded once -- and no statistics
+  const float* act_scale;
+  const float* act_shift;
+  int act_relu;
 };
 
 template <typename T> struct Mma2;
@@ -94,8 +99,11 @@ __device__ __forceinline__ void pin16(f32x4& v) { asm volatile("" : "+v"(v)); }
 
 // BNRED: the epilogue accumulates the BatchNorm-backward sums of DirectArgs::bn_* instead of output statistics (a
 // separate instantiation: the extra live registers of that epilogue must not weigh on the plain kernels; no bias)
-template <typename T, int TW, int BN, bool BRES, bool BNRED = false>
+// ACT: the output activation of DirectArgs::act_* in the epilogue (a separate instantiation as well; bf16 keeps the two
+// channel vectors in an LDS table behind the weight slots, fp32 -- one channel per lane and N tile -- in registers)
+template <typename T, int TW, int BN, bool BRES, bool BNRED = false, bool ACT = false>
 __global__ __launch_bounds__(512, 1) void conv3x3_direct_kernel(const DirectArgs a) {
+  static_assert(!(ACT && BNRED), "the output activation is a form of the plain forward");
   constexpr int VEC = ElemTraits<T>::VEC;
   constexpr int ES = (int)sizeof(T);
   constexpr int BK = 8 * VEC;
@@ -109,8 +117,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_direct_kernel(const DirectArgs
   constexpr int TN = BN / 64;             // 32-wide N tiles per wave (waves: 4 (M) x 2 (N))
   constexpr int WTN = BN / 2;
   static_assert(APW <= 9, "A patch pieces must fit the nine tap steps");
-  __shared__ __attribute__((aligned(16))) char smem[2 * A_BYTES + B_SLOTS * B_STAGE];
+  constexpr int ACT_BYTES = (ACT && sizeof(T) == 2) ? 2 * BN * 4 : 0;   // [scale x BN | shift x BN]
+  __shared__ __attribute__((aligned(16))) char smem[2 * A_BYTES + B_SLOTS * B_STAGE + ACT_BYTES];
+  static_assert(sizeof(smem) <= 160 * 1024, "LDS budget");
   char* const sB = smem + 2 * A_BYTES;
+  float* const sAct = reinterpret_cast<float*>(sB + B_SLOTS * B_STAGE);
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -314,6 +325,23 @@ __global__ __launch_bounds__(512, 1) void conv3x3_direct_kernel(const DirectArgs
     const int n = n0 + wn * WTN + j * 32 + l31;
     bv[j] = (a.bias != nullptr && n < a.Nout) ? a.bias[n] : 0.f;
   }
+  // ACT: the two channel vectors, loaded once and unconditionally (a channel beyond Nout reads channel 0) before the tiles
+  float osc[TN], osh[TN];
+  if constexpr (ACT && sizeof(T) == 4) {
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const int n = n0 + wn * WTN + j * 32 + l31;
+      osc[j] = a.act_scale[n < a.Nout ? n : 0];
+      osh[j] = a.act_shift[n < a.Nout ? n : 0];
+    }
+  }
+  if constexpr (ACT && sizeof(T) == 2) {
+    const int which = tid / BN, c = tid - which * BN;   // (2 BN <= 512 threads)
+    const float v = (which == 1 ? a.act_shift : a.act_scale)[(which < 2 && n0 + c < a.Nout) ? n0 + c : 0];
+    if (which < 2) sAct[tid] = v;
+    // executed, not just issued, before the barriers of the first tile let another wave's epilogue read the table
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  }
   // bf16 path (transposed accumulators): accumulator register r of N tile j is channel
   // wn*WTN + 32 j + (r & 3) + 8 (r >> 2) + 4 lh
   float bq[TN][16];
@@ -502,8 +530,19 @@ __global__ __launch_bounds__(512, 1) void conv3x3_direct_kernel(const DirectArgs
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             bf16x4 pk;
+            if constexpr (ACT) {
+              const f32x4 sc = *reinterpret_cast<const f32x4*>(sAct + wn * WTN + j * 32 + 8 * q + 4 * lh);
+              const f32x4 sh = *reinterpret_cast<const f32x4*>(sAct + BN + wn * WTN + j * 32 + 8 * q + 4 * lh);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) pk[e] = (bf16_t)(BNRED ? acc[i][j][4 * q + e] : acc[i][j][4 * q + e] + bq[j][4 * q + e]);
+              for (int e = 0; e < 4; ++e) {
+                float v = fmaf(acc[i][j][4 * q + e] + bq[j][4 * q + e], sc[e], sh[e]);
+                if (a.act_relu) v = fmaxf(v, 0.f);
+                pk[e] = (bf16_t)v;
+              }
+            } else {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) pk[e] = (bf16_t)(BNRED ? acc[i][j][4 * q + e] : acc[i][j][4 * q + e] + bq[j][4 * q + e]);
+            }
             *reinterpret_cast<bf16x4*>(rowp + (wn * WTN + j * 32 + 8 * q + 4 * lh) * ES) = pk;
           }
         }
@@ -559,7 +598,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_direct_kernel(const DirectArgs
               sq1[e] += dz;
               sq2[e] += dz * ((yv - bmu[e]) * bis[e]);
             }
-          } else if (dostats) {  // statistics of the stored values, pixels inside the image only
+          } else if (!ACT && dostats) {  // statistics of the stored values, pixels inside the image only
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
               const float fv = (float)vb[k].v[e];
@@ -583,11 +622,18 @@ __global__ __launch_bounds__(512, 1) void conv3x3_direct_kernel(const DirectArgs
             const int pj = (TW == 32) ? ml : (ml & 15);
             const int hh = h0 + pi, ww = w0 + pj;
             if (n < a.Nout && hh < a.H && ww < a.W) {
-              const T tv = (T)(acc[i][j][r] + bv[j]);
+              float v = acc[i][j][r] + bv[j];
+              if constexpr (ACT) {
+                v = fmaf(v, osc[j], osh[j]);
+                if (a.act_relu) v = fmaxf(v, 0.f);
+              }
+              const T tv = (T)v;
               yg[((size_t)(img * a.H + hh) * a.W + ww) * a.ldy + n] = tv;
-              const float fv = (float)tv;
-              s1[j] += fv;
-              s2[j] += fv * fv;
+              if constexpr (!ACT) {
+                const float fv = (float)tv;
+                s1[j] += fv;
+                s2[j] += fv * fv;
+              }
             }
           }
         }
@@ -1020,6 +1066,15 @@ static int direct_launch_t(const UzDirectPlan& p, const DirectArgs& a, hipStream
       return UZ_OK;
     }
   }
+  if (a.act_scale != nullptr) {
+#define UZ_ACT(TWv, BNv, RESv) hipLaunchKernelGGL((conv3x3_direct_kernel<T, TWv, BNv, RESv, false, true>), grid, block, 0, s, a)
+    if (p.bn == 64 && p.bres) { if (p.tw == 32) UZ_ACT(32, 64, true); else UZ_ACT(16, 64, true); }
+    else if (p.bn == 64) { if (p.tw == 32) UZ_ACT(32, 64, false); else UZ_ACT(16, 64, false); }
+    else { if (p.tw == 32) UZ_ACT(32, 128, false); else UZ_ACT(16, 128, false); }
+#undef UZ_ACT
+    UZ_LAUNCH_CHECK("uz_conv_igemm_bnact(direct3x3)");
+    return UZ_OK;
+  }
   if (p.bn == 64) {
     if (p.bres) {
       if (p.tw == 32) hipLaunchKernelGGL((conv3x3_direct_kernel<T, 32, 64, true>), grid, block, 0, s, a);
@@ -1038,11 +1093,11 @@ static int direct_launch_t(const UzDirectPlan& p, const DirectArgs& a, hipStream
 
 int uz_direct_launch(const uz_conv_desc* d, const UzDirectPlan& p, const void* x, const void* w,
                      const float* bias, void* y, float* stats, hipStream_t s, const UzBnRed* br, float* part,
-                     const UzXf* xf) {
+                     const UzXf* xf, const UzBnAct* ba) {
   const int es = d->dtype == UZ_BF16 ? 2 : 4;
   if (p.bres == 3) {
     UzPpPlan pp = {p.ppcfg, p.bn, p.th_n, p.tw_n, p.ntiles, p.tiles_n, p.grid_m, p.ksplit, p.cps};
-    return uz_pp_launch(d, pp, x, w, bias, y, stats, s, br, part, xf);
+    return uz_pp_launch(d, pp, x, w, bias, y, stats, s, br, part, xf, ba);
   }
   UZ_REQUIRE(xf == nullptr, "uz_conv_igemm_xf: the input transform is the ping-pong kernel's");
   UZ_REQUIRE(part == nullptr, "uz_conv_igemm(direct3x3): split-K is the ping-pong kernel's");
@@ -1053,6 +1108,11 @@ int uz_direct_launch(const uz_conv_desc* d, const UzDirectPlan& p, const void* x
   a.bn_mean = br ? br->mean : nullptr;
   a.bn_invstd = br ? br->invstd : nullptr;
   a.ld_bny = br ? br->ldy : 0;
+  a.act_scale = ba ? ba->scale : nullptr;
+  a.act_shift = ba ? ba->shift : nullptr;
+  a.act_relu = ba ? ba->relu : 0;
+  if (ba) UZ_REQUIRE(br == nullptr && p.bres != 2 && stats == nullptr && ba->scale && ba->shift,
+                     "uz_conv_igemm_bnact: direct 3x3 kernels with the workgroup-wide epilogue only, no statistics");
   if (br) UZ_REQUIRE(d->dtype == UZ_BF16 && p.bres != 2 && stats != nullptr,
                      "uz_conv_igemm_bnred: bf16 direct 3x3 kernels with LDS-staged epilogue only");
   a.x = x;

@@ -62,6 +62,11 @@ struct PpArgs {
   // patch inside LDS, so the normalised activation never exists in HBM (DoubleConv's middle tensor, common_layers.py:28-33)
   const float* xf_scale;
   const float* xf_shift;
+  // ACT (template parameter): the epilogue stores relu?(fma(acc, act_scale[co], act_shift[co])) -- the eval-mode BatchNorm
+  // [+ ReLU] of uz_bn_relu_apply on the fp32 result, rounded once -- and no statistics (uz_conv_igemm_bnact)
+  const float* act_scale;
+  const float* act_shift;
+  int act_relu;
 };
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
@@ -238,9 +243,10 @@ __device__ __forceinline__ void lds_write16u(unsigned lds_addr, const u32x4& v) 
   asm volatile("ds_write_b128 %0, %1" ::"v"(lds_addr), "v"(v) : "memory");
 }
 
-template <typename C, bool BNRED, bool SPLIT = false, bool XF = false>
+template <typename C, bool BNRED, bool SPLIT = false, bool XF = false, bool ACT = false>
 __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PpArgs a) {
   static_assert(!(BNRED && SPLIT), "the split-K form has no fused epilogue");
+  static_assert(!(ACT && (BNRED || SPLIT || XF)), "the output activation is a form of the plain forward");
   static_assert(!(BNRED && XF), "the fused BatchNorm-backward sums belong to input gradients, the input transform to forwards");
   typedef bf16_t T;
   constexpr int ES = 2, VEC = 8;
@@ -335,7 +341,16 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PpArgs a) {
   // bias table (fp32, the channels of this workgroup): the accumulators' initial value
   float* const sBias = reinterpret_cast<float*>(smem + OFF_BIAS);
   if (tid < BN) sBias[tid] = (!BNRED && !SPLIT && a.bias != nullptr && n0 + tid < a.Nout) ? a.bias[n0 + tid] : 0.f;
-  {   // running BatchNorm sums of this lane (channel chunk lane & 7 of the read-back phase): zero, in the staging strip
+  if constexpr (ACT) {
+    // (scale, shift) of this wave's 64 output channels, loaded once and unconditionally (a channel beyond Nout reads channel
+    // 0): they wait in the 16 spare bytes that end each of the 32 rows of the wave's own staging strip -- rows 0 .. 15 hold
+    // scale[4 row ..], rows 16 .. 31 shift[4 (row - 16) ..] -- which no staging write or read-back touches; no sums are
+    // parked in the strip in this form, and the LDS image stays as large as the plain kernel's
+    const int row = lane & 31;
+    const int ch = n0 + wn * 64 + 4 * (row & 15);
+    const f32x4 v = *reinterpret_cast<const f32x4*>((row < 16 ? a.act_scale : a.act_shift) + (ch < a.Nout ? ch : 0));
+    if (lane < 32) *reinterpret_cast<f32x4*>(smem + OFF_STG + wave * STG_W + row * STG_ROW + 128) = v;
+  } else {   // running BatchNorm sums of this lane (channel chunk lane & 7 of the read-back phase): zero, in the staging strip
     f32x4* sp = reinterpret_cast<f32x4*>(smem + OFF_STG + wave * STG_W + lane * 64);
     sp[0] = sp[1] = sp[2] = sp[3] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
@@ -675,7 +690,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PpArgs a) {
     const int nch = n0 + wn * 64 + cc * VEC;
     // this lane's running sums live in the staging strip between epilogues (16 registers the main loop needs)
     float sq1[VEC], sq2[VEC];
-    {
+    f32x4 asc[CT], ash[CT];   // ACT: (scale, shift) of the 4 consecutive channels this lane holds per accumulator
+    if constexpr (ACT) {
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) {
+        asc[ct] = *reinterpret_cast<const f32x4*>(stg + (4 * ct + eq) * STG_ROW + 128);
+        ash[ct] = *reinterpret_cast<const f32x4*>(stg + (16 + 4 * ct + eq) * STG_ROW + 128);
+      }
+    } else {
       const f32x4* sp = reinterpret_cast<const f32x4*>(stg + ln * 64);
       const f32x4 s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3];
 #pragma unroll
@@ -720,7 +742,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PpArgs a) {
         for (int ct = 0; ct < CT; ++ct) {
           bf16x4 pk;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) pk[e] = (bf16_t)acc[2 * r + h][ct][e];
+          for (int e = 0; e < 4; ++e) {
+            float v = acc[2 * r + h][ct][e];   // (the bias was the accumulator's initial value)
+            if constexpr (ACT) {
+              v = fmaf(v, asc[ct][e], ash[ct][e]);
+              if (a.act_relu) v = fmaxf(v, 0.f);
+            }
+            pk[e] = (bf16_t)v;
+          }
           *reinterpret_cast<bf16x4*>(stg + (16 * h + e15) * STG_ROW + (16 * ct + 4 * eq) * ES) = pk;
         }
       // read back: lane = (pixel (lane >> 3) + 8 k, channel chunk lane & 7); LDS operations of one wave execute in order
@@ -737,7 +766,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PpArgs a) {
         // operations per wave and tile, which the counted waits of the next tile's first phases allow for
         const unsigned off = inside ? (unsigned)((((im * a.H + hh) * a.W + ww) * a.ldy + nch) * ES) : OOB;
         __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&vb[k]), yr, off, 0, 0);
-        if (inside) {
+        if (!ACT && inside) {
           if constexpr (BNRED) {
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
@@ -757,7 +786,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PpArgs a) {
         }
       }
     }
-    {
+    if constexpr (!ACT) {
       f32x4* sp = reinterpret_cast<f32x4*>(stg + ln * 64);
       sp[0] = f32x4{sq1[0], sq1[1], sq1[2], sq1[3]};
       sp[1] = f32x4{sq1[4], sq1[5], sq1[6], sq1[7]};
@@ -799,7 +828,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PpArgs a) {
   }
 
   // ---- statistics: fixed-order sum over the lanes that own a channel chunk ---------------------------------------------------
-  if (!SPLIT && a.stats != nullptr) {
+  if (!SPLIT && !ACT && a.stats != nullptr) {
     wait_vmcnt<0>();
     __syncthreads();
     // thread `th` left its sums [2][VEC] at strip(th >> 6) + (th & 63) * 64
@@ -913,8 +942,15 @@ int uz_pp_xf_channels(const UzPpPlan& p) {
 }
 
 int uz_pp_launch(const uz_conv_desc* d, const UzPpPlan& p, const void* x, const void* w, const float* bias, void* y,
-                 float* stats, hipStream_t s, const UzBnRed* br, float* part, const UzXf* xf) {
+                 float* stats, hipStream_t s, const UzBnRed* br, float* part, const UzXf* xf, const UzBnAct* ba) {
   PpArgs a;
+  a.act_scale = ba ? ba->scale : nullptr;
+  a.act_shift = ba ? ba->shift : nullptr;
+  a.act_relu = ba ? ba->relu : 0;
+  if (ba)
+    UZ_REQUIRE(br == nullptr && part == nullptr && xf == nullptr && stats == nullptr && ba->scale && ba->shift &&
+                   ((uintptr_t)ba->scale & 15) == 0 && ((uintptr_t)ba->shift & 15) == 0,
+               "uz_conv_igemm_bnact(direct3x3 ping-pong): plain forward only, 16-byte aligned scale / shift");
   a.part = part;
   a.cps = p.cps;
   a.xf_scale = xf ? xf->scale : nullptr;
@@ -964,10 +1000,11 @@ int uz_pp_launch(const uz_conv_desc* d, const UzPpPlan& p, const void* x, const 
     UZ_LAUNCH_CHECK("uz_conv_igemm_xf(direct3x3 ping-pong)");
     return UZ_OK;
   }
-#define UZ_PP_GO(CFG)                                                                          \
-  do {                                                                                         \
-    if (br) hipLaunchKernelGGL((conv3x3_pp_kernel<CFG, true>), grid, block, 0, s, a);          \
-    else hipLaunchKernelGGL((conv3x3_pp_kernel<CFG, false>), grid, block, 0, s, a);            \
+#define UZ_PP_GO(CFG)                                                                                          \
+  do {                                                                                                         \
+    if (ba) hipLaunchKernelGGL((conv3x3_pp_kernel<CFG, false, false, false, true>), grid, block, 0, s, a);     \
+    else if (br) hipLaunchKernelGGL((conv3x3_pp_kernel<CFG, true>), grid, block, 0, s, a);                     \
+    else hipLaunchKernelGGL((conv3x3_pp_kernel<CFG, false>), grid, block, 0, s, a);                            \
   } while (0)
   switch (p.cfg) {
     case UZ_PP_512: UZ_PP_GO(Cfg512); break;

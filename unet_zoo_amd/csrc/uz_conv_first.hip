@@ -42,6 +42,11 @@ struct CfArgs {
   const double* bn_sums;   // [2][Cout] totals (uz_bn_bwd_finalize)
   double inv_count;
   int ldyr;
+  // forward with the eval-mode BatchNorm [+ ReLU] in the epilogue (uz_conv3x3_first_fwd_bnact): the stored value is
+  // relu?(fma(acc + bias, act_scale[co], act_shift[co])), rounded once; no statistics
+  const float* act_scale;
+  const float* act_shift;
+  int act_relu;
 };
 
 __device__ __forceinline__ float round_bf16(float v) { return (float)(bf16_t)v; }
@@ -79,14 +84,15 @@ __device__ __forceinline__ void halo_store(float* sx, const float (&h)[4], unsig
 static_assert(3 * PH * PW <= 4 * 256, "four halo elements per thread");
 
 // ---- forward: one workgroup (4 waves) per 8 x 32 tile; wave w owns rows 2w, 2w + 1; CT = Cout / 32 ------------------------
-template <int CT>
+template <int CT, bool ACT = false>
 __global__ __launch_bounds__(256) void conv_first_fwd_kernel(const CfArgs a) {
   // (the bias is added in fp32 from an LDS table when the accumulators are rounded: carried in two spare K slots as bf16 value +
   // bf16 remainder it was off by 2^-17 relative, enough to round 2e-4 of the outputs the other way)
   __shared__ float sx[3 * PH * PW];
   __shared__ __attribute__((aligned(16))) float sbias[64];
+  __shared__ __attribute__((aligned(16))) float sact[ACT ? 128 : 4];   // ACT: [scale x 64 | shift x 64]
   __shared__ __attribute__((aligned(16))) char sstg[4][32 * STG];
-  __shared__ float sred[4][2][CT * 32];
+  __shared__ float sred[ACT ? 1 : 4][2][CT * 32];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int px = lane & 31, b = lane >> 5;
   const int per = a.th_n * a.tw_n;
@@ -95,6 +101,10 @@ __global__ __launch_bounds__(256) void conv_first_fwd_kernel(const CfArgs a) {
   unsigned hmask = 0;
   if ((int)blockIdx.x < a.ntiles) hmask = halo_fetch(a, hreg, blockIdx.x, tid);
   if (tid < 64) sbias[tid] = (a.bias != nullptr && tid < a.Cout) ? a.bias[tid] : 0.f;
+  if constexpr (ACT) {   // the two channel vectors, once, unconditionally, in front of the tiles (the tile loop opens with a barrier)
+    const float v = (tid < 64 ? a.act_scale : a.act_shift)[(tid & 63) < a.Cout ? (tid & 63) : 0];
+    if (tid < 128) sact[tid] = v;
+  }
 
   // weights as the row operand: lane (co = 32 t + lane % 32, K block b) holds w[co][16 kh + 8 b + i], zero beyond K
   bf16x8 wfr[CT][2];
@@ -175,8 +185,19 @@ __global__ __launch_bounds__(256) void conv_first_fwd_kernel(const CfArgs a) {
         for (int g4 = 0; g4 < 4; ++g4) {
           const f32x4 bq = *reinterpret_cast<const f32x4*>(sbias + 32 * t + 8 * g4 + 4 * b);
           bf16x4 o;
+          if constexpr (ACT) {
+            const f32x4 sc = *reinterpret_cast<const f32x4*>(sact + 32 * t + 8 * g4 + 4 * b);
+            const f32x4 sh = *reinterpret_cast<const f32x4*>(sact + 64 + 32 * t + 8 * g4 + 4 * b);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (bf16_t)(acc[4 * g4 + e] + bq[e]);
+            for (int e = 0; e < 4; ++e) {
+              float v = fmaf(acc[4 * g4 + e] + bq[e], sc[e], sh[e]);
+              if (a.act_relu) v = fmaxf(v, 0.f);
+              o[e] = (bf16_t)v;
+            }
+          } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = (bf16_t)(acc[4 * g4 + e] + bq[e]);
+          }
           *reinterpret_cast<bf16x4*>(stg + px * STG + (32 * t + 8 * g4 + 4 * b) * 2) = o;
         }
       }
@@ -191,18 +212,20 @@ __global__ __launch_bounds__(256) void conv_first_fwd_kernel(const CfArgs a) {
         const int gw = w0 + p;
         if (gh < a.H && gw < a.W && ch * 8 < a.Cout) {
           *reinterpret_cast<bf16x8*>(yg + (((size_t)img * a.H + gh) * a.W + gw) * a.ldy + ch * 8) = v;
+          if constexpr (!ACT) {
 #pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float f = (float)v[e];
-            st1[e] += f;
-            st2[e] += f * f;
+            for (int e = 0; e < 8; ++e) {
+              const float f = (float)v[e];
+              st1[e] += f;
+              st2[e] += f * f;
+            }
           }
         }
       }
       __builtin_amdgcn_wave_barrier();   // the strip is rewritten by the next row
     }
   }
-  if (a.stats == nullptr) return;
+  if (ACT || a.stats == nullptr) return;
   // ---- this workgroup's partial row: the PPI lanes of a wave that read chunk ch, then the four waves, in fixed order
   __syncthreads();
   float* red = reinterpret_cast<float*>(sstg[wave]);   // [64 lanes][16 sums] = 4 KB of the wave's 4.5 KB strip
@@ -482,6 +505,29 @@ extern "C" int uz_conv3x3_first_fwd(int dtype, const float* x, int N, int C, int
   if (Cout == 64) hipLaunchKernelGGL(conv_first_fwd_kernel<2>, dim3(grid), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(conv_first_fwd_kernel<1>, dim3(grid), dim3(256), 0, s, a);
   UZ_LAUNCH_CHECK("uz_conv3x3_first_fwd");
+  return UZ_OK;
+}
+
+extern "C" int uz_conv3x3_first_fwd_bnact(int dtype, const float* x, int N, int C, int H, int W, const float* w,
+                                          const float* bias, int Cout, const float* out_scale, const float* out_shift,
+                                          int relu, void* y, int ldy, void* stream) {
+  const int rc = check(dtype, N, C, H, W, Cout, ldy, "uz_conv3x3_first_fwd_bnact");
+  if (rc != UZ_OK) return rc;
+  UZ_REQUIRE(x && w && y && out_scale && out_shift && ((uintptr_t)y & 15) == 0, "uz_conv3x3_first_fwd_bnact: null / unaligned pointer");
+  CfArgs a = {};
+  a.x = x;
+  a.w = w;
+  a.bias = bias;
+  a.y = y;
+  a.act_scale = out_scale;
+  a.act_shift = out_shift;
+  a.act_relu = relu ? 1 : 0;
+  fill(a, N, C, H, W, Cout, ldy);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int grid = first_fwd_grid(a.ntiles);
+  if (Cout == 64) hipLaunchKernelGGL((conv_first_fwd_kernel<2, true>), dim3(grid), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((conv_first_fwd_kernel<1, true>), dim3(grid), dim3(256), 0, s, a);
+  UZ_LAUNCH_CHECK("uz_conv3x3_first_fwd_bnact");
   return UZ_OK;
 }
 

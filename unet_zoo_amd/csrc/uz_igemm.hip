@@ -31,6 +31,11 @@ struct IgemmArgs {
   // part[z][M][Nout]; igemm_split_reduce_kernel sums them in fixed order (deterministic)
   float* part;
   int tpg;
+  // ACT (template parameter, uz_conv_igemm_bnact): the epilogue stores relu?(fma(acc + bias, act_scale[n], act_shift[n])) --
+  // the eval-mode BatchNorm [+ ReLU] of uz_bn_relu_apply on the fp32 result, rounded once -- and no statistics
+  const float* act_scale;
+  const float* act_shift;
+  int act_relu;
 };
 
 template <typename T> struct Mma;
@@ -51,7 +56,7 @@ template <> struct Mma<float> {
   }
 };
 
-template <typename T, int BM, int BN, int WM, int WN>
+template <typename T, int BM, int BN, int WM, int WN, bool ACT = false>
 __global__ __launch_bounds__(256, 2) void igemm_kernel(const IgemmArgs a) {
   constexpr int VEC = ElemTraits<T>::VEC;
   constexpr int BK = 8 * VEC;  // elements per 128-byte row slab
@@ -82,6 +87,17 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const IgemmArgs a) {
   float s1[TN], s2[TN];
 #pragma unroll
   for (int i = 0; i < TN; ++i) s1[i] = s2[i] = 0.f;
+  // ACT: the two channel vectors of this lane's columns, loaded once and unconditionally (a column beyond Nout reads
+  // column 0) before the tiles
+  float osc[TN], osh[TN];
+  if constexpr (ACT) {
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const int n = n0 + wn * WTN + j * 32 + l31;
+      osc[j] = a.act_scale[n < a.Nout ? n : 0];
+      osh[j] = a.act_shift[n < a.Nout ? n : 0];
+    }
+  }
 
   const int cpt = (a.Cin + BK - 1) / BK;  // K-steps per tap; the last slab may be partial (zeros)
   const int tap_lo = a.part != nullptr ? (int)blockIdx.z * a.tpg : 0;
@@ -192,7 +208,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const IgemmArgs a) {
       __syncthreads();
     }
 
-    if (a.part != nullptr) {  // split: raw fp32 partial tile, finished by the reduce kernel
+    if (!ACT && a.part != nullptr) {  // split: raw fp32 partial tile, finished by the reduce kernel
       float* __restrict__ pz = a.part + (size_t)blockIdx.z * a.M * a.Nout;
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
@@ -224,9 +240,14 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const IgemmArgs a) {
         for (int r = 0; r < 16; ++r) {
           const int m = m0 + wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
           if (m < a.M && nok) {
-            const T tv = (T)(acc[i][j][r] + bv);
+            float v = acc[i][j][r] + bv;
+            if constexpr (ACT) {
+              v = fmaf(v, osc[j], osh[j]);
+              if (a.act_relu) v = fmaxf(v, 0.f);
+            }
+            const T tv = (T)v;
             size_t o;
-            if (a.store == UZ_STORE_PLAIN) {
+            if (ACT || a.store == UZ_STORE_PLAIN) {
               o = (size_t)m * a.ldy + n;
             } else {
               const int img = m / HW;
@@ -238,16 +259,18 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const IgemmArgs a) {
               o = opix * a.ldy + co;
             }
             yg[o] = tv;
-            const float fv = (float)tv;
-            s1[j] += fv;
-            s2[j] += fv * fv;
+            if constexpr (!ACT) {
+              const float fv = (float)tv;
+              s1[j] += fv;
+              s2[j] += fv * fv;
+            }
           }
         }
       }
     }
   }
 
-  if (a.stats != nullptr && a.part == nullptr) {
+  if (!ACT && a.stats != nullptr && a.part == nullptr) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       s1[j] += __shfl_xor(s1[j], 32);
@@ -452,6 +475,12 @@ int make_plan(const uz_conv_desc* d, Plan* p) {
 template <typename T>
 int launch(const uz_conv_desc* d, const Plan& p, const IgemmArgs& a, hipStream_t s) {
   dim3 grid(p.grid_m, p.tiles_n, a.part != nullptr ? p.split : 1), block(256);
+  if (a.act_scale != nullptr) {
+    if (p.bn == 64) hipLaunchKernelGGL((igemm_kernel<T, 128, 64, 2, 2, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((igemm_kernel<T, 128, 128, 2, 2, true>), grid, block, 0, s, a);
+    UZ_LAUNCH_CHECK("uz_conv_igemm_bnact");
+    return UZ_OK;
+  }
   if (p.bn == 64) {
     hipLaunchKernelGGL((igemm_kernel<T, 128, 64, 2, 2>), grid, block, 0, s, a);
   } else {
@@ -724,6 +753,75 @@ extern "C" int uz_conv_igemm_ws(const uz_conv_desc* d, const void* x, const void
   a.tiles_m = p.tiles_m;
   a.part = (p.split > 1 && workspace != nullptr) ? static_cast<float*>(workspace) : nullptr;
   a.tpg = (d->ntaps + p.split - 1) / p.split;
+  a.act_scale = nullptr;
+  a.act_shift = nullptr;
+  a.act_relu = 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
+  return d->dtype == UZ_BF16 ? launch<bf16_t>(d, p, a, s) : launch<float>(d, p, a, s);
+}
+
+// ---- convolution whose epilogue applies the eval-mode BatchNorm [+ ReLU] behind it (include/unetzoo_hip.h) --------------
+extern "C" int uz_conv_igemm_bnact_supported(const uz_conv_desc* d) {
+  Plan p;
+  if (d == nullptr || make_plan(d, &p) != UZ_OK) return 0;
+  if (d->store_mode != UZ_STORE_PLAIN || !(d->taps_mode == UZ_TAPS_CONV || d->taps_mode == UZ_TAPS_CONV_UP2)) return 0;
+  UzDirectPlan dp;
+  UzGemmPlan gp;
+  if (uz_direct_plan(d, &dp)) {
+    if (dp.bres == 2) return 0;                    // weights-in-registers kernel: its register budget has no room (DESIGN)
+    if (dp.bres == 3 && dp.ksplit > 1) return 0;   // split-K plan: the result is formed by the reduce pass
+    return 1;
+  }
+  if (uz_gemm_dma_plan(d, &gp)) return 0;          // 1x1 on the LDS-DMA GEMM
+  return p.split > 1 ? 0 : 1;                      // generic kernel, unless its plan splits the taps over a workspace
+}
+
+extern "C" int uz_conv_igemm_bnact(const uz_conv_desc* d, const void* x, const void* w_packed, const float* bias,
+                                   const float* out_scale, const float* out_shift, int relu, void* y, void* stream) {
+  Plan p;
+  const int rc = make_plan(d, &p);
+  if (rc != UZ_OK) return rc;
+  UZ_REQUIRE(x && w_packed && y && out_scale && out_shift, "uz_conv_igemm_bnact: null pointer");
+  UZ_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)w_packed & 15) == 0 && ((uintptr_t)y & 15) == 0 &&
+                 ((uintptr_t)out_scale & 15) == 0 && ((uintptr_t)out_shift & 15) == 0,
+             "uz_conv_igemm_bnact: x / w / y / out_scale / out_shift must be 16-byte aligned");
+  if (!uz_conv_igemm_bnact_supported(d)) {
+    uz_set_error("uz_conv_igemm_bnact: only plain-store 3x3 / 1x1 problems of the direct kernels with a workgroup-wide "
+                 "epilogue and of the generic kernel, without a split plan (ask uz_conv_igemm_bnact_supported)");
+    return UZ_ENOTIMPL;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const UzBnAct ba = {out_scale, out_shift, relu ? 1 : 0};
+  UzDirectPlan dp;
+  if (uz_direct_plan(d, &dp)) return uz_direct_launch(d, dp, x, w_packed, bias, y, nullptr, s, nullptr, nullptr, nullptr, &ba);
+  IgemmArgs a;
+  a.x = x;
+  a.w = w_packed;
+  a.y = y;
+  a.bias = bias;
+  a.stats = nullptr;
+  a.M = d->N * d->H * d->W;
+  a.H = d->H;
+  a.W = d->W;
+  a.Hin = d->Hin;
+  a.Win = d->Win;
+  a.Cin = d->Cin;
+  a.ldx = d->ldx;
+  a.Nout = d->Nout;
+  a.ldy = d->ldy;
+  a.K = d->ntaps * d->Cin;
+  a.ntaps = d->ntaps;
+  a.mode = d->taps_mode;
+  a.dil = d->dil;
+  a.store = UZ_STORE_PLAIN;
+  a.Co = d->Co;
+  a.Hout = 2 * d->H;
+  a.Wout = 2 * d->W;
+  a.tiles_m = p.tiles_m;
+  a.part = nullptr;
+  a.tpg = d->ntaps;
+  a.act_scale = out_scale;
+  a.act_shift = out_shift;
+  a.act_relu = relu ? 1 : 0;
   return d->dtype == UZ_BF16 ? launch<bf16_t>(d, p, a, s) : launch<float>(d, p, a, s);
 }

@@ -171,10 +171,23 @@ class Engine:
     # last ~100 MB are still in the Infinity Cache; the pass then ends at the low addresses, where the next (ascending)
     # convolution starts reading (class-level: tools/ab_step.py times both ways)
     reverse_element_passes = True
+    # inference only (model.eval(), no tape): a Conv -> BatchNorm -> ReLU layer without pool / residual is ONE launch -- the
+    # running-statistics (scale, shift) are constants known before the convolution, whose epilogue forms the activation from
+    # its fp32 result (uz_conv_igemm_bnact, uz_conv3x3_first_fwd_bnact): the raw output is neither written nor re-read, and the
+    # bf16 activation is rounded once instead of twice.  OFF by default: bf16 eval numbers then stay what they were
+    # (GraphedEval(fold_bn=True) asks for it per engine, through the constructor); fp32 is bit-identical either way.  An
+    # engine counts in `folded_layers` / `unfolded_layers` the layers of its forward that took the one-launch route / stayed
+    # on two launches while the switch was on (tests read them: a layer that silently falls back shows there)
+    fold_bn_eval = False
 
     def __init__(self, dtype: torch.dtype, device: torch.device, training: bool, record: bool,
                  grad_sink: Optional[Callable[[nn.Parameter, torch.Tensor], None]] = None,
-                 pack_cache: Optional[PackCache] = None, grads_in_place: bool = False):
+                 pack_cache: Optional[PackCache] = None, grads_in_place: bool = False,
+                 fold_bn_eval: Optional[bool] = None):
+        if fold_bn_eval is not None:      # this engine's own setting instead of the class switch
+            self.fold_bn_eval = bool(fold_bn_eval)
+        self.folded_layers = 0
+        self.unfolded_layers = 0
         self.dtype = dtype
         self.device = device
         self.training = training
@@ -403,6 +416,13 @@ class Engine:
             wp = self._pack(conv.weight, L.PACK_CONV_FWD)
             ntaps = 9 if conv.kernel_size == (3, 3) else 1     # 1x1 + BN + ReLU: unet_transformer.py:150-177
             assert ntaps == 9 or not upsample
+        if self.fold_bn_eval and not self.training and not self.record:
+            act = self._conv_bn_relu_folded(x, conv, bn, out, image, wp, ntaps, dil, tmode, relu, N, H, W) \
+                if (not pool and residual is None and stat_repeat == 1 and xf is None) else None
+            if act is not None:
+                self.folded_layers += 1
+                return act, None
+            self.unfolded_layers += 1
         y = self.new_act(N, H, W, Cout)
         bias = conv.bias.detach() if conv.bias is not None else None
         if image is not None:
@@ -552,6 +572,26 @@ class Engine:
 
             self.tape.append(bwd)
         return act, pooled
+
+    def _conv_bn_relu_folded(self, x, conv: nn.Conv2d, bn: nn.BatchNorm2d, out: Optional[Act], image, wp, ntaps: int,
+                             dil: int, tmode: int, relu: bool, N: int, H: int, W: int) -> Optional[Act]:
+        """conv_bn_relu's one-launch eval route (Engine.fold_bn_eval): the activation, or None when no kernel with the
+        output activation takes the layer (the caller then runs the two launches).  The activation is a real tensor: not
+        lazy, no bn_src; `out` is honoured."""
+        Cout = conv.out_channels
+        ld = out.ld if out is not None else Cout
+        if Cout % 4 != 0:      # the kernels read the two vectors in 16-byte pieces
+            return None
+        if image is None and not ops.conv_bnact_supported(x, Cout, ld, ntaps=ntaps, dil=dil, taps_mode=tmode):
+            return None
+        v2 = ops.bn_eval_scale(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps)
+        act = out if out is not None else self.new_act(N, H, W, Cout)
+        bias = conv.bias.detach() if conv.bias is not None else None
+        if image is not None:
+            ops.conv_first_fwd_bnact(image, conv.weight.detach(), bias, v2[0], v2[1], relu, act)
+        else:
+            ops.conv_igemm_bnact(x, wp, bias, v2[0], v2[1], relu, act, ntaps=ntaps, dil=dil, taps_mode=tmode)
+        return act
 
     def attention_gate(self, g: Act, x: Act, blk: nn.Module, out: Act) -> Act:
         """out = x * sigmoid(BN(W_psi relu(BN(W_g g) + BN(W_x x)))), written into its concat slot.

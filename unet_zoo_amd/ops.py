@@ -392,6 +392,52 @@ def conv_igemm(x: Act, w_packed: torch.Tensor, bias: Optional[torch.Tensor], y: 
     return stats
 
 
+def _bnact_desc(x: Act, nout: int, ldy: int, ntaps: int, dil: int, taps_mode: int):
+    H, W = (2 * x.H, 2 * x.W) if taps_mode == L.TAPS_CONV_UP2 else (x.H, x.W)
+    return L.ConvDesc(L.dtype_code(x.dtype), x.N, H, W, x.H, x.W, x.C, x.ld, nout, ldy, ntaps, taps_mode, dil,
+                      L.STORE_PLAIN, 0, 0, 0)
+
+
+def conv_bnact_supported(x: Act, nout: int, ldy: int, *, ntaps: int, dil: int = 1, taps_mode: int = L.TAPS_CONV) -> bool:
+    """whether uz_conv_igemm_bnact takes the convolution of x to nout channels (eval-mode BatchNorm [+ ReLU] in the epilogue)"""
+    if taps_mode not in (L.TAPS_CONV, L.TAPS_CONV_UP2):
+        return False
+    d = _bnact_desc(x, nout, ldy, ntaps, dil, taps_mode)
+    return bool(L.load().uz_conv_igemm_bnact_supported(byref(d)))
+
+
+def conv_igemm_bnact(x: Act, w_packed: torch.Tensor, bias: Optional[torch.Tensor], scale: torch.Tensor, shift: torch.Tensor,
+                     relu: bool, y: Act, *, ntaps: int, dil: int = 1, taps_mode: int = L.TAPS_CONV) -> None:
+    """y = relu?(fma(conv(x, w) + bias, scale, shift)) in one launch, rounded once (uz_conv_igemm_bnact): the convolution with
+    the eval-mode BatchNorm [+ ReLU] behind it; the caller has asked conv_bnact_supported() first.  No fallback."""
+    L.require_cuda(x.buf, w_packed, y.buf, scale, shift)
+    d = _bnact_desc(x, y.C, y.ld, ntaps, dil, taps_mode)
+    assert w_packed.dtype == x.dtype and y.dtype == x.dtype and (y.N, y.H, y.W) == (d.N, d.H, d.W)
+    assert w_packed.shape == (d.Nout, ntaps * x.C), (tuple(w_packed.shape), d.Nout, ntaps, x.C)
+    assert scale.dtype == shift.dtype == torch.float32 and scale.numel() == shift.numel() == d.Nout
+    assert scale.is_contiguous() and shift.is_contiguous()
+    M, K, es = d.N * d.H * d.W, ntaps * x.C, x.buf.element_size()
+    with _Timed(conv_kernel_name(d) + "_bnact", 2.0 * M * d.Nout * K, es * (x.P * x.C + M * d.Nout + d.Nout * K)):
+        L.check(L.load().uz_conv_igemm_bnact(byref(d), x.ptr(), w_packed.data_ptr(), _p(bias), scale.data_ptr(),
+                                             shift.data_ptr(), 1 if relu else 0, y.ptr(), L.stream_ptr()), "uz_conv_igemm_bnact")
+
+
+def conv_first_fwd_bnact(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], scale: torch.Tensor,
+                         shift: torch.Tensor, relu: bool, y: Act) -> None:
+    """conv_first_fwd with the eval-mode BatchNorm [+ ReLU] in the epilogue (uz_conv3x3_first_fwd_bnact); no statistics"""
+    L.require_cuda(x, w, y.buf, scale, shift)
+    assert x.dtype == torch.float32 and x.is_contiguous() and w.dtype == torch.float32 and w.is_contiguous()
+    N, C, H, W = x.shape
+    Cout = w.shape[0]
+    assert (y.N, y.H, y.W, y.C) == (N, H, W, Cout) and tuple(w.shape) == (Cout, C, 3, 3)
+    assert scale.dtype == shift.dtype == torch.float32 and scale.numel() == shift.numel() == Cout
+    assert scale.is_contiguous() and shift.is_contiguous()
+    with _Timed("conv3x3_first_bf16_bnact", 2.0 * N * H * W * 9 * C * Cout, 4.0 * x.numel() + 2.0 * y.P * Cout):
+        L.check(L.load().uz_conv3x3_first_fwd_bnact(L.dtype_code(y.dtype), x.data_ptr(), N, C, H, W, w.data_ptr(), _p(bias), Cout,
+                                                    scale.data_ptr(), shift.data_ptr(), 1 if relu else 0, y.ptr(), y.ld,
+                                                    L.stream_ptr()), "uz_conv3x3_first_fwd_bnact")
+
+
 def conv_xform_supported(x: Act, nout: int, ldy: int, *, upsample: bool = False) -> bool:
     """whether uz_conv_igemm_xf takes the 3x3 convolution of x (channels, pixel grid, run dtype) to nout channels"""
     H, W = (2 * x.H, 2 * x.W) if upsample else (x.H, x.W)
