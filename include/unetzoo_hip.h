@@ -607,7 +607,9 @@ int uz_ln_head_bwd(const uz_ln_desc* d, const void* x, const float* gamma, const
  *   S_ij = (scale q_i . k_j) / max(|scale q_i| |k_j|, 1e-6) / max(tau[h][i][j], 0.01) + bias[h][i][j]
  *          (- 100 when the shifted-window region ids differ, :214-236);  out_i = softmax_j(S) v
  * tau: (heads, Nt, Nt) parameter (Nt >= ws*ws), bias: (heads, ws*ws, ws*ws) fp32 = cpb MLP output.
- * lse: (B*nW, heads, ws*ws) row log-sum-exp kept for the backward.  head_dim must be 32, ws <= 8. */
+ * lse: (B*nW, heads, ws*ws) row log-sum-exp kept for the backward.  head_dim must be 32, ws <= 16: windows of up to 64
+ * tokens (ws <= 8) hold the window in one tile, windows of 65 .. 256 tokens (ws 9 .. 16) walk it in 32 x 32 tiles of
+ * the score matrix (uz_winattn_wide.hip); ws > 16 fails ("exceeds 16x16"). */
 typedef struct uz_winattn_desc {
   int dtype, B, H, W, C, heads, ws, shift, Nt;
   int ldq, ldo;
@@ -616,7 +618,7 @@ typedef struct uz_winattn_desc {
 int uz_winattn_fwd(const uz_winattn_desc* d, const void* qkv, const float* tau, const float* bias,
                    void* out, float* lse, void* stream);
 /* Continuous position bias (:121-125, Mlp_Relu :58-72): bias[h][r] = fc2(relu(fc1(idx[r]))) over the
- * R = N*N log-spaced offsets idx (R, 2); w1 (hidden, 2), b1 (hidden), w2 (heads, hidden), b2 (heads), fp32.
+ * R = N*N log-spaced offsets idx (R, 2) (any R: 65 536 at ws 16); w1 (hidden, 2), b1 (hidden), w2 (heads, hidden), b2 (heads), fp32.
  * Backward from G = d bias (heads, R): gradients of the four parameter tensors, overwritten. */
 int uz_cpb_fwd(const float* idx, const float* w1, const float* b1, const float* w2, const float* b2, int R,
                int hidden, int heads, float* bias, void* stream);
@@ -642,9 +644,12 @@ typedef struct {
 int uz_cpb_fwd_batched(const uz_cpb_item* items, int n, void* stream);
 long long uz_cpb_bwd_batched_workspace_bytes(const uz_cpb_item* items, int n);
 int uz_cpb_bwd_batched(const uz_cpb_item* items, int n, float* workspace, void* stream);
-int uz_winattn_bwd_rows(const uz_winattn_desc* d); /* rows of `partial`; <0 on error */
+/* rows of `partial`; <0 on error.  A function of the descriptor and the CU reserve only.  For windows of more than 64
+ * tokens the rows (1.5 MiB each at ws 16 with 3 heads) are capped so that the buffer stays within 64 MiB. */
+int uz_winattn_bwd_rows(const uz_winattn_desc* d);
 /* dqkv (P, 3C) fully written; partial[row][2][heads][N][N]: sums over the row's windows of dS (-> d bias)
- * and of d tau (zero where tau < 0.01); add the rows with uz_sum_rows() / uz_sum_rows_f32(). */
+ * and of d tau (zero where tau < 0.01), every element written (no zero-fill needed); add the rows with uz_sum_rows() /
+ * uz_sum_rows_f32(). */
 int uz_winattn_bwd(const uz_winattn_desc* d, const void* qkv, const float* tau, const float* bias,
                    const void* out, const float* lse, const void* dout, int lddo, void* dqkv, int lddq,
                    float* partial, void* stream);

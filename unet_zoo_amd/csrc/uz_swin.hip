@@ -638,23 +638,8 @@ __global__ __launch_bounds__(1024) void ln_head_finalize_kernel(const float* __r
 // ---------------------------------------------------------------------------------------------
 // Window attention.
 // ---------------------------------------------------------------------------------------------
-struct AttnArgs {
-  const void* qkv;    // [P][3C]: per token [3][heads][32]
-  void* out;          // [P][C]   (bwd: the forward output, read)
-  float* lse;         // [B*nW][heads][N] row log-sum-exp
-  const float* tau;   // [heads][Nt][Nt] (Nt = window_size^2 of the parameter, N <= Nt used)
-  const float* bias;  // [heads][N][N]
-  const void* dout;   // bwd: gradient of out [P][C]
-  void* dqkv;         // bwd: gradient of qkv [P][3C]
-  float* partial;     // bwd: [gridDim.x][2][heads][N][N] sums of dS (dbias) and d(tau)
-  int B, H, W, C, heads, ws, shift, Nt;
-  int ldq, ldo, lddo, lddq;
-  float scale;
-  int flags;          // ablation build only (UZ_KFLAGS)
-};
-
 constexpr int AD = 32;       // head dimension (embed_dim 96 / 3 heads, doubled together: always 32)
-constexpr int AN = 64;       // max tokens per window (window_size <= 8)
+constexpr int AN = 64;       // max tokens per window of the kernels in this file (window_size <= 8; wider: uz_winattn_wide.hip)
 constexpr int ARS = AD + 4;  // LDS row stride of the [token][32] tiles: rows stay 16-byte aligned, so a row
                              // (read by all lanes at once = broadcast) costs 8 ds_read_b128, not 32 ds_read_b32
 constexpr int ANS = AN + 1;  // LDS row stride of the [N][N] matrices
@@ -704,26 +689,6 @@ __device__ __forceinline__ void scale_axpy32(float c, float w, const float* x, f
     y[e] = r.x;
     y[e + 1] = r.y;
   }
-}
-
-struct WinTok {
-  int tok;   // row of the token tensor
-  int cnt;   // region id of the shifted-window mask
-};
-__device__ __forceinline__ WinTok win_token(const AttnArgs& a, int win, int i) {
-  const int nwx = a.W / a.ws, nwy = a.H / a.ws, nW = nwx * nwy;
-  const int b = win / nW, wi = win - b * nW, wy = wi / nwx, wx = wi - wy * nwx;
-  const int iy = i / a.ws, ix = i - iy * a.ws;
-  const int hs = wy * a.ws + iy, wsx = wx * a.ws + ix;  // coordinates in the rolled image
-  int h = hs + a.shift, w = wsx + a.shift;
-  if (h >= a.H) h -= a.H;
-  if (w >= a.W) w -= a.W;
-  WinTok t;
-  t.tok = (b * a.H + h) * a.W + w;
-  const int hid = hs < a.H - a.ws ? 0 : (hs < a.H - a.shift ? 1 : 2);
-  const int wid = wsx < a.W - a.ws ? 0 : (wsx < a.W - a.shift ? 1 : 2);
-  t.cnt = a.shift > 0 ? hid * 3 + wid : 0;
-  return t;
 }
 
 template <typename T> __device__ __forceinline__ void load_head(const T* p, float* f) {  // 32 values
@@ -1855,7 +1820,7 @@ __global__ __launch_bounds__(256) void winattn_bwd_kernel(const AttnArgs a) {
 // ---------------------------------------------------------------------------------------------
 // Continuous position bias: bias[h][r] = b2[h] + sum_k w2[h][k] relu(w1[k][0] x0(r) + w1[k][1] x1(r) + b1[k])
 // over the R = N*N log-spaced offsets (get_continuous_relative_position_bias, swin_unet_v2.py:121-125 with
-// Mlp_Relu :58-72).  A function of parameters only; R <= 4096, hidden = 256, heads <= 32.
+// Mlp_Relu :58-72).  A function of parameters only; hidden = 256, heads <= 32, any R (4096 at window 8, 65 536 at window 16).
 // ---------------------------------------------------------------------------------------------
 constexpr int CPB_MAXH = 32;
 constexpr int CPB_MAXHID = 512;
@@ -1989,7 +1954,7 @@ __global__ __launch_bounds__(1024) void cpb_bwd_kernel(const float* __restrict__
 }
 
 // ---- all position-bias MLPs of a model in one launch ------------------------------------------------
-// The MLPs are tiny (R <= 4096 offsets, 256 hidden units, <= 32 heads) and a function of parameters only, so
+// The MLPs are tiny (R <= 4096 offsets up to window 8, 65 536 at window 16; 256 hidden units, <= 32 heads) and a function of parameters only, so
 // a model's 14 of them are evaluated together at the start of the forward and differentiated together at the
 // end of the backward: 2 + 1 launches instead of 28, and the backward reads each G once (cpb_bwd_kernel above
 // re-reads it per hidden unit: 22 us per module, bound by L2).
@@ -2403,8 +2368,8 @@ static int attn_check(const char* fn, const uz_winattn_desc* d) {
   UZ_REQUIRE(d->dtype == UZ_F32 || d->dtype == UZ_BF16, "%s: bad dtype", fn);
   UZ_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->heads > 0 && d->C == d->heads * AD,
              "%s: needs head_dim 32 (C=%d, heads=%d)", fn, d->C, d->heads);
-  UZ_REQUIRE(d->ws >= 1 && d->ws * d->ws <= AN && d->H % d->ws == 0 && d->W % d->ws == 0,
-             "%s: window %d does not tile %dx%d (or exceeds 8x8)", fn, d->ws, d->H, d->W);
+  UZ_REQUIRE(d->ws >= 1 && d->ws * d->ws <= UZ_WIDE_MAXN && d->H % d->ws == 0 && d->W % d->ws == 0,
+             "%s: window %d does not tile %dx%d (or exceeds 16x16)", fn, d->ws, d->H, d->W);
   UZ_REQUIRE(d->shift >= 0 && d->shift < d->ws && d->Nt >= d->ws * d->ws, "%s: bad shift / tau size", fn);
   const int vec = d->dtype == UZ_BF16 ? 8 : 4;
   UZ_REQUIRE(d->ldq % vec == 0 && d->ldq >= 3 * d->C && d->ldo % vec == 0 && d->ldo >= d->C, "%s: bad strides", fn);
@@ -2441,6 +2406,19 @@ static int attn_mfma_grid_x(const uz_winattn_desc* d) {
 }
 static bool attn_bwd_mfma(const uz_winattn_desc* d) { return d->dtype == UZ_BF16 && !(uz_tune_flags() & 0x2000); }
 
+// windows of more than AN tokens run on the tile-walking kernels of uz_winattn_wide.hip
+static bool attn_wide(const uz_winattn_desc* d) { return d->ws * d->ws > AN; }
+// Their d(bias) / d(tau) rows are [2][heads][N][N] fp32 each (1.5 MiB at N = 256, 3 heads): the backward's grid -- one row per
+// workgroup column -- is capped so that the launch's partial buffer stays within UZ_WIDE_PARTIAL_BYTES.  A function of the
+// descriptor and the CU reserve only.
+static int attn_wide_bwd_grid_x(const uz_winattn_desc* d) {
+  const int fit = attn_grid_x(d, d->dtype == UZ_BF16 ? UZ_WIDE_SLOTS_BWD_BF16 : UZ_WIDE_SLOTS_BWD_F32);
+  const long long N = (long long)d->ws * d->ws, row_bytes = 2LL * d->heads * N * N * (long long)sizeof(float);
+  long long cap = UZ_WIDE_PARTIAL_BYTES / row_bytes;
+  if (cap < 1) cap = 1;
+  return (int)(fit < cap ? fit : cap);
+}
+
 extern "C" int uz_winattn_fwd(const uz_winattn_desc* d, const void* qkv, const float* tau, const float* bias,
                               void* out, float* lse, void* stream) {
   const int rc = attn_check("uz_winattn_fwd", d);
@@ -2450,6 +2428,7 @@ extern "C" int uz_winattn_fwd(const uz_winattn_desc* d, const void* qkv, const f
   a.qkv = qkv; a.out = out; a.lse = lse; a.tau = tau; a.bias = bias;
   a.B = d->B; a.H = d->H; a.W = d->W; a.C = d->C; a.heads = d->heads; a.ws = d->ws; a.shift = d->shift; a.Nt = d->Nt;
   a.ldq = d->ldq; a.ldo = d->ldo; a.scale = d->scale; a.flags = uz_tune_flags();
+  if (attn_wide(d)) return uz_winattn_wide_fwd_launch(d->dtype, a, attn_grid_x(d, UZ_WIDE_SLOTS_FWD), (hipStream_t)stream);
   const dim3 grid(attn_grid_x(d, ATTN_SLOTS_FWD), d->heads), block(256);
   if (d->dtype == UZ_BF16 && !(uz_tune_flags() & 0x1000)) {
     // matrix-core path: one wave per (window, head), four per workgroup
@@ -2470,6 +2449,7 @@ extern "C" int uz_winattn_fwd(const uz_winattn_desc* d, const void* qkv, const f
 extern "C" int uz_winattn_bwd_rows(const uz_winattn_desc* d) {
   const int rc = attn_check("uz_winattn_bwd_rows", d);
   if (rc != UZ_OK) return rc;
+  if (attn_wide(d)) return attn_wide_bwd_grid_x(d);
   return attn_grid_x(d, attn_bwd_mfma(d) ? ATTN_SLOTS_BWD_MFMA : ATTN_SLOTS_BWD);
 }
 
@@ -2486,6 +2466,7 @@ extern "C" int uz_winattn_bwd(const uz_winattn_desc* d, const void* qkv, const f
   a.dout = dout; a.dqkv = dqkv; a.partial = partial;
   a.B = d->B; a.H = d->H; a.W = d->W; a.C = d->C; a.heads = d->heads; a.ws = d->ws; a.shift = d->shift; a.Nt = d->Nt;
   a.ldq = d->ldq; a.ldo = d->ldo; a.lddo = lddo; a.lddq = lddq; a.scale = d->scale; a.flags = uz_tune_flags();
+  if (attn_wide(d)) return uz_winattn_wide_bwd_launch(d->dtype, a, attn_wide_bwd_grid_x(d), (hipStream_t)stream);
   const dim3 grid(attn_grid_x(d, attn_bwd_mfma(d) ? ATTN_SLOTS_BWD_MFMA : ATTN_SLOTS_BWD), d->heads), block(256);
   if (attn_bwd_mfma(d)) {
     hipLaunchKernelGGL(winattn_bwd_mfma_kernel, grid, block, 0, (hipStream_t)stream, a);

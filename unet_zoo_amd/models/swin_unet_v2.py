@@ -106,8 +106,8 @@ class WindowAttention(nn.Module):
         self.dim, self.window_size, self.num_heads = dim, window_size, num_heads
         if dim % num_heads:
             raise ValueError(f"dim {dim} is not divisible by num_heads {num_heads}")
-        # head_dim 32 runs on the fused MFMA / VALU kernels; other widths and attention dropout take the engine's
-        # library-GEMM window core.  (qk_scale cancels in q.k / (|q||k|) except inside the 1e-6 clamp.)
+        # head_dim 32 and windows of up to 16x16 run on the fused MFMA / VALU kernels; the engine refuses other widths, wider
+        # windows and attention dropout in training.  (qk_scale cancels in q.k / (|q||k|) except inside the 1e-6 clamp.)
         self.scale = qk_scale or (dim // num_heads) ** -0.5
         ch, cw = torch.arange(window_size[0]), torch.arange(window_size[1])
         coords = torch.stack(torch.meshgrid([ch, cw], indexing="ij")).flatten(1)
@@ -360,8 +360,8 @@ class SwinTransformerSys(HipModule):
         for lvl in range(nl - 1):
             cats.append(eng.new_cat(N, R[0] >> lvl, R[1] >> lvl, (E << lvl, E << lvl)))
         DropPath.draw_all(self, N, eng.device, eng.training)
-        # (only the blocks whose window core runs on the fused kernels: Engine.window_attention sends the others --
-        # head_dim != 32, attention dropout in training -- through its library-GEMM core, position MLP included)
+        # (only the blocks whose window core the kernels take: Engine.window_attention refuses the others -- head_dim != 32,
+        # attention dropout in training -- before it would read a bias)
         eng.position_biases([(m.attn, m.window_size) for m in self.modules() if isinstance(m, SwinTransformerBlock)
                              and m.dim // m.num_heads == 32 and not (eng.training and m.attn.attn_drop.p > 0)])
         skip0 = cats[0][1][1]

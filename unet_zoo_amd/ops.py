@@ -1194,7 +1194,11 @@ def winattn_fwd(qkv: Act, tau: torch.Tensor, bias: torch.Tensor, out: Act, heads
     nwin = qkv.N * (qkv.H // ws) * (qkv.W // ws)
     lse = torch.empty((nwin, heads, ws * ws), dtype=torch.float32, device=qkv.buf.device)
     assert tau.dtype == torch.float32 and tau.is_contiguous() and bias.shape == (heads, ws * ws, ws * ws)
-    with _Timed("winattn_fwd", 4.0 * qkv.P * ws * ws * out.C, qkv.buf.element_size() * qkv.P * out.C * 4):
+    N = ws * ws
+    nbytes = qkv.buf.element_size() * qkv.P * out.C * 4
+    if N > 64:      # the tile-walking kernels read tau and bias per (window, head) instead of holding them in registers
+        nbytes += 8 * nwin * heads * N * N
+    with _Timed("winattn_fwd", 4.0 * qkv.P * N * out.C, nbytes):
         L.check(L.load().uz_winattn_fwd(byref(d), qkv.ptr(), tau.data_ptr(), bias.data_ptr(), out.ptr(), lse.data_ptr(),
                                         L.stream_ptr()), "uz_winattn_fwd")
     return lse
@@ -1211,7 +1215,13 @@ def winattn_bwd(qkv: Act, tau: torch.Tensor, bias: torch.Tensor, out: Act, lse: 
     rows = L.check_count(lib.uz_winattn_bwd_rows(byref(d)), "uz_winattn_bwd_rows")
     N = ws * ws
     part = torch.empty((rows, 2, heads, N, N), dtype=torch.float32, device=qkv.buf.device)
-    with _Timed("winattn_bwd", 10.0 * qkv.P * N * out.C, qkv.buf.element_size() * qkv.P * out.C * 8):
+    flops, nbytes = 10.0 * qkv.P * N * out.C, qkv.buf.element_size() * qkv.P * out.C * 8
+    if N > 64:
+        # the tile-walking kernel forms S and dP in both passes (14 products of P x N x C / 2 each way), reads tau and bias
+        # in both and adds dS / d(tau) into its partial row in memory (read + write of two tables per (window, head))
+        nwin = qkv.N * (qkv.H // ws) * (qkv.W // ws)
+        flops, nbytes = 14.0 * qkv.P * N * out.C, nbytes + (16 + 16) * nwin * heads * N * N
+    with _Timed("winattn_bwd", flops, nbytes):
         L.check(lib.uz_winattn_bwd(byref(d), qkv.ptr(), tau.data_ptr(), bias.data_ptr(), out.ptr(), lse.data_ptr(),
                                    dout.ptr(), dout.ld, dqkv.ptr(), dqkv.ld, part.data_ptr(), L.stream_ptr()),
                 "uz_winattn_bwd")
