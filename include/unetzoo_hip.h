@@ -609,7 +609,7 @@ int uz_ln_head_bwd(const uz_ln_desc* d, const void* x, const float* gamma, const
  * tau: (heads, Nt, Nt) parameter (Nt >= ws*ws), bias: (heads, ws*ws, ws*ws) fp32 = cpb MLP output.
  * lse: (B*nW, heads, ws*ws) row log-sum-exp kept for the backward.  head_dim must be 32, ws <= 16: windows of up to 64
  * tokens (ws <= 8) hold the window in one tile, windows of 65 .. 256 tokens (ws 9 .. 16) walk it in 32 x 32 tiles of
- * the score matrix (uz_winattn_wide.hip); ws > 16 fails ("exceeds 16x16"). */
+ * the score matrix (both in uz_winattn.hip); ws > 16 fails ("exceeds 16x16"). */
 typedef struct uz_winattn_desc {
   int dtype, B, H, W, C, heads, ws, shift, Nt;
   int ldq, ldo;

@@ -12,12 +12,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import kres  # noqa: E402
 
-# kernels allowed to carry scratch, with the bound they are allowed: (substring of the demangled name) -> bytes per lane
-ALLOW_SCRATCH = {
-    # fp32-parity window attention forward (VALU softmax beside MFMA, 325 registers): 32 B, outside every timed path
-    "winattn_fwd_mfma_kernel": 32,
-}
-
 
 @pytest.fixture(scope="module")
 def kernels():
@@ -32,8 +26,7 @@ def test_no_kernel_spills_vector_registers_or_uses_scratch(kernels):
     for k in kernels:
         scratch = k.get("private_segment_fixed_size", 0)
         spills = k.get("vgpr_spill_count", 0)
-        allowed = max([v for s, v in ALLOW_SCRATCH.items() if s in k["demangled"]] or [0])
-        if scratch > allowed or (spills and not allowed):
+        if scratch or spills:
             bad.append(f"{k['file']}: {kres.short(k['demangled'])}: {spills} VGPRs spilled, {scratch} B scratch")
     assert not bad, "kernels with spills / scratch:\n" + "\n".join(bad)
 

@@ -16,6 +16,7 @@ from oracle import torch_ref
 from unet_zoo_amd import _lib as L
 from unet_zoo_amd import ops
 from unet_zoo_amd.ops import Act, act_from_nchw
+from winattn_ref import attention_core_ref as _attention_core_ref  # tests/winattn_ref.py (pytest puts this directory on sys.path)
 
 DEV = "cuda"
 DTYPES = [torch.float32, torch.bfloat16]
@@ -168,29 +169,6 @@ def test_layernorm_patch_expand_addressing(dt, r, c):
     dgam, dbet = ops.layernorm_bwd(xa, gd, stats, tokens_to_act(dy, dt), dx, mode=L.LN_EXPAND, r=r)
     assert relerr(act_to_tokens(dx), x.grad) < (1e-5 if dt == torch.float32 else 1e-2)
     assert relerr(dgam.cpu(), gamma.grad) < 1e-4 and relerr(dbet.cpu(), beta.grad) < 1e-4
-
-
-def _attention_core_ref(qkv, tau, bias, heads, ws, shift):
-    """the reference's roll -> window_partition -> cosine attention -> window_reverse -> roll back
-    (swin_unet_v2.py:127-159, 246-262) on a (B, H, W, 3C) qkv tensor, without the qkv / proj Linears"""
-    B, H, W, C3 = qkv.shape
-    C = C3 // 3
-    d = C // heads
-    xs = torch.roll(qkv, shifts=(-shift, -shift), dims=(1, 2)) if shift > 0 else qkv
-    xw = xs.view(B, H // ws, ws, W // ws, ws, C3).permute(0, 1, 3, 2, 4, 5).reshape(-1, ws * ws, C3)
-    B_, N, _ = xw.shape
-    t = xw.reshape(B_, N, 3, heads, d).permute(2, 0, 3, 1, 4)
-    q, k, v = t[0] * d ** -0.5, t[1], t[2]
-    attn = torch.einsum("bhqd,bhkd->bhqk", q, k) / torch.maximum(
-        q.norm(dim=-1, keepdim=True) * k.norm(dim=-1, keepdim=True).transpose(-2, -1), torch.tensor(1e-6))
-    attn = attn / torch.clip(tau.unsqueeze(0)[:, :, :N, :N], min=0.01) + bias.unsqueeze(0)
-    if shift > 0:
-        mask = torch_ref.swin_attention_mask(H, W, ws, shift)
-        nW = mask.shape[0]
-        attn = (attn.view(B_ // nW, nW, heads, N, N) + mask.unsqueeze(1).unsqueeze(0)).view(-1, heads, N, N)
-    o = (attn.softmax(-1) @ v).transpose(1, 2).reshape(B_, N, C)
-    o = o.view(B, H // ws, W // ws, ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, C)
-    return torch.roll(o, shifts=(shift, shift), dims=(1, 2)) if shift > 0 else o
 
 
 @pytest.mark.parametrize("dt", DTYPES)

@@ -1,4 +1,4 @@
-"""GPU: swin_unet_v2 with windows above 8x8 (window_size 9 .. 16: 81 .. 256 tokens per window, uz_winattn_wide.hip).
+"""GPU: swin_unet_v2 with windows above 8x8 (window_size 9 .. 16: 81 .. 256 tokens per window, the wide kernels of uz_winattn.hip).
 
 1. fp32 train step + eval at 128 / window 16 and 96 / window 12 against the reference's goldens
    (tools/gen_golden_swin_wide.py), with the bounds of test_swin_gpu.py::test_swin_fp32_step_matches_reference_golden.  The

@@ -1,7 +1,7 @@
-"""GPU: the window-attention kernels of uz_swin.hip where a workgroup walks SEVERAL windows.
+"""GPU: the window-attention kernels of uz_winattn.hip where a workgroup walks SEVERAL windows.
 
 The four kernels (winattn_fwd_kernel / winattn_bwd_kernel in fp32, winattn_fwd_mfma2_kernel / winattn_bwd_mfma_kernel in
-bf16) are persistent: attn_grid_fit() caps the x-grid at 256 * slots / heads workgroups (slots = resident workgroups per CU,
+bf16) are persistent: attn_grid_x() caps the x-grid at 256 * slots / heads workgroups (slots = resident workgroups per CU,
 1 .. 3) and a workgroup handles windows blockIdx.x, blockIdx.x + gridDim.x, ...  The other kernel-level tests have at most
 8 windows -- one trip through that loop.  Here every case has more windows than any of the four grids holds, and is held
   1. against a float64 restatement of the reference (roll -> partition -> cosine attention -> reverse -> roll back) and its
@@ -23,11 +23,12 @@ from oracle import torch_ref
 from unet_zoo_amd import _lib as L
 from unet_zoo_amd import ops
 from unet_zoo_amd.ops import Act
+from winattn_ref import attention_core_ref as _attention_core_ref, grid as _grid  # tests/winattn_ref.py (pytest puts this directory on sys.path)
 
 DEV = "cuda"
 DTYPES = [torch.float32, torch.bfloat16]
 NUM_CU = 256
-# resident workgroups per CU of the kernel that serves (direction, dtype): ATTN_SLOTS_* of uz_swin.hip
+# resident workgroups per CU of the kernel that serves (direction, dtype): ATTN_SLOTS_* of uz_winattn.hip
 SLOTS = {("fwd", torch.float32): 2, ("fwd", torch.bfloat16): 3, ("bwd", torch.float32): 1, ("bwd", torch.bfloat16): 2}
 
 # (heads, ws, shift, B, H, W, Nt); windows per workgroup at full chip as "grid: count x windows", in the order
@@ -66,36 +67,6 @@ def rnd(dt, t):
 
 def relerr(a, b):
     return ((a.double() - b.double()).abs().max() / (b.double().abs().max() + 1e-30)).item()
-
-
-def _grid(nwin, heads, slots, num_cu=NUM_CU):
-    """attn_grid_fit() of uz_swin.hip: the windows are dealt evenly over at most num_cu * slots / heads workgroups"""
-    cap = max(1, num_cu * slots // heads)
-    per = -(-nwin // cap)
-    return -(-nwin // per)
-
-
-def _attention_core_ref(qkv, tau, bias, heads, ws, shift):
-    """the reference's roll -> window_partition -> cosine attention -> window_reverse -> roll back
-    (swin_unet_v2.py:127-159, 246-262) on a (B, H, W, 3C) qkv tensor, without the qkv / proj Linears"""
-    B, H, W, C3 = qkv.shape
-    C = C3 // 3
-    d = C // heads
-    xs = torch.roll(qkv, shifts=(-shift, -shift), dims=(1, 2)) if shift > 0 else qkv
-    xw = xs.view(B, H // ws, ws, W // ws, ws, C3).permute(0, 1, 3, 2, 4, 5).reshape(-1, ws * ws, C3)
-    B_, N, _ = xw.shape
-    t = xw.reshape(B_, N, 3, heads, d).permute(2, 0, 3, 1, 4)
-    q, k, v = t[0] * d ** -0.5, t[1], t[2]
-    attn = torch.einsum("bhqd,bhkd->bhqk", q, k) / torch.maximum(
-        q.norm(dim=-1, keepdim=True) * k.norm(dim=-1, keepdim=True).transpose(-2, -1), torch.tensor(1e-6))
-    attn = attn / torch.clip(tau.unsqueeze(0)[:, :, :N, :N], min=0.01) + bias.unsqueeze(0)
-    if shift > 0:
-        mask = torch_ref.swin_attention_mask(H, W, ws, shift)
-        nW = mask.shape[0]
-        attn = (attn.view(B_ // nW, nW, heads, N, N) + mask.unsqueeze(1).unsqueeze(0)).view(-1, heads, N, N)
-    o = (attn.softmax(-1) @ v).transpose(1, 2).reshape(B_, N, C)
-    o = o.view(B, H // ws, W // ws, ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, C)
-    return torch.roll(o, shifts=(shift, shift), dims=(1, 2)) if shift > 0 else o
 
 
 def _reference64(qkv, tau, bias, dout, case):

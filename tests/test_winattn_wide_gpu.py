@@ -1,4 +1,4 @@
-"""GPU: the window-attention kernels of uz_winattn_wide.hip, windows of 65 .. 256 tokens (window_size 9 .. 16).
+"""GPU: the window-attention wide kernels of uz_winattn.hip, windows of 65 .. 256 tokens (window_size 9 .. 16).
 
 Kernel level, in the scheme of tests/test_swin_gpu.py::test_window_attention_core_forward_backward: the reference is a
 float64 restatement of the reference model's roll -> partition -> cosine attention -> reverse -> roll back and its autograd
@@ -20,11 +20,12 @@ from oracle import torch_ref
 from unet_zoo_amd import _lib as L
 from unet_zoo_amd import ops
 from unet_zoo_amd.ops import Act
+from winattn_ref import attention_core_ref as _attention_core_ref, grid as _grid  # tests/winattn_ref.py (pytest puts this directory on sys.path)
 
 DEV = "cuda"
 DTYPES = [torch.float32, torch.bfloat16]
 NUM_CU = 256
-# resident workgroups per CU the grids are sized by: UZ_WIDE_SLOTS_* of csrc/uz_common.h
+# resident workgroups per CU the grids are sized by: UZ_WIDE_SLOTS_* of csrc/uz_winattn.hip
 SLOTS = {("fwd", torch.float32): 2, ("fwd", torch.bfloat16): 2, ("bwd", torch.float32): 1, ("bwd", torch.bfloat16): 2}
 PARTIAL_BYTES = 64 << 20     # UZ_WIDE_PARTIAL_BYTES: cap of one launch's d(bias) / d(tau) partial rows
 
@@ -52,29 +53,6 @@ def rnd(dt, t):
 
 def relerr(a, b):
     return ((a.double() - b.double()).abs().max() / (b.double().abs().max() + 1e-30)).item()
-
-
-def _attention_core_ref(qkv, tau, bias, heads, ws, shift):
-    """the reference's roll -> window_partition -> cosine attention -> window_reverse -> roll back
-    (swin_unet_v2.py:127-159, 246-262) on a (B, H, W, 3C) qkv tensor, without the qkv / proj Linears"""
-    B, H, W, C3 = qkv.shape
-    C = C3 // 3
-    d = C // heads
-    xs = torch.roll(qkv, shifts=(-shift, -shift), dims=(1, 2)) if shift > 0 else qkv
-    xw = xs.view(B, H // ws, ws, W // ws, ws, C3).permute(0, 1, 3, 2, 4, 5).reshape(-1, ws * ws, C3)
-    B_, N, _ = xw.shape
-    t = xw.reshape(B_, N, 3, heads, d).permute(2, 0, 3, 1, 4)
-    q, k, v = t[0] * d ** -0.5, t[1], t[2]
-    attn = torch.einsum("bhqd,bhkd->bhqk", q, k) / torch.maximum(
-        q.norm(dim=-1, keepdim=True) * k.norm(dim=-1, keepdim=True).transpose(-2, -1), torch.tensor(1e-6))
-    attn = attn / torch.clip(tau.unsqueeze(0)[:, :, :N, :N], min=0.01) + bias.unsqueeze(0)
-    if shift > 0:
-        mask = torch_ref.swin_attention_mask(H, W, ws, shift)
-        nW = mask.shape[0]
-        attn = (attn.view(B_ // nW, nW, heads, N, N) + mask.unsqueeze(1).unsqueeze(0)).view(-1, heads, N, N)
-    o = (attn.softmax(-1) @ v).transpose(1, 2).reshape(B_, N, C)
-    o = o.view(B, H // ws, W // ws, ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, C)
-    return torch.roll(o, shifts=(shift, shift), dims=(1, 2)) if shift > 0 else o
 
 
 def _operands(case, dt):
@@ -158,13 +136,6 @@ def test_wide_window_attention_core_forward_backward(dt, case):
 
 # ---- the walk --------------------------------------------------------------------------------------------------
 WALK = (12, 64, 64, 3, 16, 8, 256)       # 192 windows of 256 tokens
-
-
-def _grid(nwin, heads, slots, num_cu=NUM_CU):
-    """attn_grid_fit() of uz_swin.hip: the windows are dealt evenly over at most num_cu * slots / heads workgroups"""
-    cap = max(1, num_cu * slots // heads)
-    per = -(-nwin // cap)
-    return -(-nwin // per)
 
 
 def _rows(nwin, heads, N, slots, num_cu=NUM_CU):

@@ -9,7 +9,7 @@
 hipcc cross-compiles gfx950 without a GPU (`--cuda-device-only -S`); the numbers are the `amdhsa.kernels` entries of the
 emitted assembly (`.vgpr_count` includes the accumulator registers, `.vgpr_spill_count`, `.private_segment_fixed_size` =
 scratch bytes per lane), i.e. what the loader will allocate -- not the remarks of an analysis pass.
-`tests/test_kernel_resources.py` runs `collect()` over the tree and fails on any spill outside its allow-list: round 4
+`tests/test_kernel_resources.py` runs `collect()` over the tree and fails on any spill or scratch: round 4
 shipped a 105-register spill on the ConvTranspose input-gradient GEMM that one look at this table would have caught.
 """
 import concurrent.futures

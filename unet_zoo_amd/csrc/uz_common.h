@@ -249,49 +249,3 @@ long long uz_gemm_dma_workspace_bytes(const uz_conv_desc* d);   // fp32 partial 
 int uz_gemm_dma_launch(const uz_conv_desc* d, const UzGemmPlan& p, const void* x, const void* w,
                        const float* bias, void* y, float* stats, hipStream_t s, const void* res = nullptr,
                        int ldres = 0, const UzBnRed* br = nullptr, float* part = nullptr);
-
-// ---- window attention (uz_swin.hip: windows of up to 64 tokens; uz_winattn_wide.hip: 65 .. 256 tokens) -------------------
-struct AttnArgs {
-  const void* qkv;    // [P][3C]: per token [3][heads][32]
-  void* out;          // [P][C]   (bwd: the forward output, read)
-  float* lse;         // [B*nW][heads][N] row log-sum-exp
-  const float* tau;   // [heads][Nt][Nt] (Nt = window_size^2 of the parameter, N <= Nt used)
-  const float* bias;  // [heads][N][N]
-  const void* dout;   // bwd: gradient of out [P][C]
-  void* dqkv;         // bwd: gradient of qkv [P][3C]
-  float* partial;     // bwd: [gridDim.x][2][heads][N][N] sums of dS (dbias) and d(tau)
-  int B, H, W, C, heads, ws, shift, Nt;
-  int ldq, ldo, lddo, lddq;
-  float scale;
-  int flags;          // ablation build only (UZ_KFLAGS)
-};
-
-struct WinTok {
-  int tok;   // row of the token tensor
-  int cnt;   // region id of the shifted-window mask
-};
-__device__ __forceinline__ WinTok win_token(const AttnArgs& a, int win, int i) {
-  const int nwx = a.W / a.ws, nwy = a.H / a.ws, nW = nwx * nwy;
-  const int b = win / nW, wi = win - b * nW, wy = wi / nwx, wx = wi - wy * nwx;
-  const int iy = i / a.ws, ix = i - iy * a.ws;
-  const int hs = wy * a.ws + iy, wsx = wx * a.ws + ix;  // coordinates in the rolled image
-  int h = hs + a.shift, w = wsx + a.shift;
-  if (h >= a.H) h -= a.H;
-  if (w >= a.W) w -= a.W;
-  WinTok t;
-  t.tok = (b * a.H + h) * a.W + w;
-  const int hid = hs < a.H - a.ws ? 0 : (hs < a.H - a.shift ? 1 : 2);
-  const int wid = wsx < a.W - a.ws ? 0 : (wsx < a.W - a.shift ? 1 : 2);
-  t.cnt = a.shift > 0 ? hid * 3 + wid : 0;
-  return t;
-}
-
-// wide windows, 64 < N = ws^2 <= 256 (uz_winattn_wide.hip); uz_winattn_fwd / _bwd / _bwd_rows dispatch here.
-// Resident workgroups per CU the grids are sized by (registers / LDS of the kernels; tests/test_winattn_wide_resources.py):
-constexpr int UZ_WIDE_MAXN = 256;
-constexpr int UZ_WIDE_SLOTS_FWD = 2;        // winattn_wide_fwd_kernel<T>
-constexpr int UZ_WIDE_SLOTS_BWD_BF16 = 2;   // winattn_wide_bwd_kernel<bf16_t>: 56 KB LDS
-constexpr int UZ_WIDE_SLOTS_BWD_F32 = 1;    // winattn_wide_bwd_kernel<float>: 106 KB LDS
-constexpr long long UZ_WIDE_PARTIAL_BYTES = 64LL << 20;   // cap of one launch's d(bias) / d(tau) partial rows
-int uz_winattn_wide_fwd_launch(int dtype, const AttnArgs& a, int grid_x, hipStream_t s);
-int uz_winattn_wide_bwd_launch(int dtype, const AttnArgs& a, int grid_x, hipStream_t s);
