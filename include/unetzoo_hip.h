@@ -732,6 +732,50 @@ int uz_bce_dice(const float* logits, const float* target, long long n, float* dl
                 void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * BCE + a region term (soft Dice / Tversky / focal Tversky) over several output maps at once.  uz_region_loss.hip
+ * Per map (logits x, target t, n fp32 elements each, p = sigmoid(x)); the flattened map is cut into `groups` contiguous
+ * chunks of n / groups elements (1: the batch, N: per image, N * K: per channel):
+ *   BCE    = mean_i [ (1 - t_i) x_i + (1 + (pos_weight - 1) t_i) softplus(-x_i) ]         (ATen's stable form)
+ *   TI_g   = (I_g + s) / (I_g + alpha (S_g - I_g) + beta (T_g - I_g) + s),   I = sum p t, S = sum p, T = sum t over chunk g
+ *   region = mean_g (1 - TI_g)^gamma                  (1 - TI_g formed as (alpha (S - I) + beta (T - I)) / denominator;
+ *                                                       gamma == 1 takes no power)
+ *   out2[0] = sum_m items[m].weight * (w_bce * BCE_m + w_region * region_m)
+ *   out2[1] = the thresholded Dice METRIC of map `metric_item`, exactly as uz_bce_dice defines it
+ *   items[m].dlogits (nullable) = d(out2[0]) / d(items[m].logits)
+ * alpha = beta = 0.5, s = s' / 2 is the soft Dice (2 I + s') / (S + T + s').
+ * `items` is a HOST array of n_items <= UZ_REGION_MAX_ITEMS entries, copied into the kernel arguments as
+ * uz_colsum_batched does with its items: no table upload, so a call can be captured into a hipGraph whatever tensors it
+ * names, and the host sees whether any gradient is asked for.  All maps of a call share n, groups and the target's layout.
+ * Launches, whatever n_items is: (1) one row of six doubles per workgroup (sum bce, sum p t, sum p, sum t, sum [x > 0] t,
+ * sum [x > 0]), every workgroup inside one chunk of one map; (2) one workgroup totals the rows in a fixed order, forms
+ * TI_g, the loss, the Dice and per chunk the coefficients (u_g, v_g) of d(loss)/d(p_i) = u_g t_i + v_g; (3) the gradient
+ *   dlogits_i = weight * [ w_bce / n * (p_i (1 + (pos_weight - 1) t_i) - pos_weight t_i) + (u_g t_i + v_g) p_i (1 - p_i) ]
+ * -- not launched when every dlogits is NULL.  No atomics, no memset, no host read; the workspace is written before it is
+ * read in every call; two calls on the same inputs give the same bits.  16-byte loads when n / groups is a multiple of 4
+ * and every pointer is 16-byte aligned, scalar loads otherwise (chosen here, on the host).
+ * UZ_EINVAL before any launch: null descriptor / items / out2 / workspace / logits / target, n <= 0, groups < 1 or not
+ * dividing n, n_items outside [1, UZ_REGION_MAX_ITEMS], metric_item outside [0, n_items), smooth <= 0, gamma < 1,
+ * alpha / beta / w_bce / w_region / an item's weight negative, w_bce = w_region = 0, pos_weight <= 0, a workspace that
+ * is not 16-byte aligned. */
+#define UZ_REGION_MAX_ITEMS 64
+typedef struct uz_region_item {
+  const float* logits;
+  const float* target;
+  float* dlogits; /* nullable */
+  float weight;
+} uz_region_item;
+typedef struct uz_region_desc {
+  int n_items;
+  long long n; /* elements per map */
+  int groups;  /* per map; divides n */
+  float w_bce, w_region, alpha, beta, smooth, gamma, pos_weight;
+  int metric_item;
+} uz_region_desc;
+long long uz_region_loss_workspace_bytes(const uz_region_desc* d); /* < 0: refused */
+int uz_region_loss(const uz_region_desc* d, const uz_region_item* items, float* out2 /* loss, dice */, void* workspace,
+                   void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Bias gradients of a whole backward pass (or phase) in two launches.  uz_colsum.hip
  * out_i[c] = sum_p x_i[p*ld + c] (fp32) for n tensors of the run dtype: what `uz_colsum_ws` computes for one
  * nn.Linear / Conv2d bias (db = sum over tokens of the output gradient), for all of them at once; `items` is a

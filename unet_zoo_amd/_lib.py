@@ -54,6 +54,7 @@ EXPORTS = (
     "uz_conv5x5_grid_m", "uz_conv5x5", "uz_wgrad5x5_workspace_bytes", "uz_wgrad5x5",
     "uz_bn_elu_apply", "uz_bn_elu_bwd_rows", "uz_bn_elu_bwd_reduce", "uz_bn_elu_bwd_apply",
     "uz_conv_igemm_bnact_supported", "uz_conv_igemm_bnact", "uz_conv3x3_first_fwd_bnact",
+    "uz_region_loss_workspace_bytes", "uz_region_loss",
 )
 
 
@@ -140,6 +141,21 @@ class PackItem(Structure):
 class Pack3x3Item(Structure):
     _fields_ = [("src", c_void_p), ("dst_fwd", c_void_p), ("dst_dgrad", c_void_p), ("Co", c_int), ("Ci", c_int),
                 ("tile_begin", c_int), ("pad_", c_int)]
+
+
+REGION_MAX_ITEMS = 64
+
+
+class RegionItem(Structure):
+    """uz_region_item: one output map of a uz_region_loss call"""
+    _fields_ = [("logits", c_void_p), ("target", c_void_p), ("dlogits", c_void_p), ("weight", c_float)]
+
+
+class RegionDesc(Structure):
+    """uz_region_desc"""
+    _fields_ = [("n_items", c_int), ("n", ctypes.c_longlong), ("groups", c_int)] \
+        + [(n, c_float) for n in ("w_bce", "w_region", "alpha", "beta", "smooth", "gamma", "pos_weight")] \
+        + [("metric_item", c_int)]
 
 
 class HipLibraryError(RuntimeError):
@@ -320,6 +336,8 @@ def load():
     lib.uz_bn_elu_bwd_rows.argtypes = [POINTER(BnEluBwdDesc)]
     lib.uz_bn_elu_bwd_reduce.argtypes = [POINTER(BnEluBwdDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.uz_bn_elu_bwd_apply.argtypes = [POINTER(BnEluBwdDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.uz_region_loss_workspace_bytes.argtypes = [POINTER(RegionDesc)]
+    lib.uz_region_loss.argtypes = [POINTER(RegionDesc), POINTER(RegionItem), vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("uz_last_error_string", "uz_source_hash"):
@@ -346,6 +364,18 @@ def check_count(rc: int, what: str) -> int:
     if rc < 0:
         _fail(rc, what)
     return rc
+
+
+def region_loss_workspace_bytes(desc: "RegionDesc") -> int:
+    """uz_region_loss_workspace_bytes(): bytes of workspace a uz_region_loss call with this descriptor needs"""
+    return check_count(load().uz_region_loss_workspace_bytes(ctypes.byref(desc)), "uz_region_loss_workspace_bytes")
+
+
+def region_loss(desc: "RegionDesc", items, out2: torch.Tensor, workspace: torch.Tensor) -> None:
+    """uz_region_loss() on the current stream: `items` is a ctypes array of RegionItem (a HOST table, copied into the
+    kernel arguments), out2 a 2-element fp32 device tensor (loss, dice).  Every call of the loss goes through here."""
+    check(load().uz_region_loss(ctypes.byref(desc), items, out2.data_ptr(), workspace.data_ptr(), stream_ptr()),
+          "uz_region_loss")
 
 
 def set_cu_reserve(n: int) -> None:

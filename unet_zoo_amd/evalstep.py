@@ -40,7 +40,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from .engine import Engine
-from .loss import loss_and_dice
+from .loss import RegionLoss, loss_and_dice
 from .step import CAPTURE_MODE, _check_capture, _new_graph, _unwrap
 
 
@@ -50,13 +50,20 @@ class _EvalGraph:
 
 
 class GraphedEval:
-    def __init__(self, model: nn.Module, criterion: Union[str, Callable] = "bce_dice", *, fold_bn: bool = False):
+    def __init__(self, model: nn.Module, criterion: Union[str, RegionLoss, Callable] = "bce_dice", *, fold_bn: bool = False):
         self.model = _unwrap(model)
         if isinstance(criterion, str):
             if criterion != "bce_dice":
                 raise ValueError(f"unknown built-in criterion {criterion!r}; pass 'bce_dice' or a callable")
             self._fused_loss = True
             self._loss_fn = None
+            self._fused = loss_and_dice
+        elif isinstance(criterion, RegionLoss):
+            # uz_region_loss: deterministic, no library reduction -- inside the graph, where "bce_dice" sits (two launches: no
+            # gradient is asked for); with several ranks each evaluates its own shard, so reduce="batch" is per shard
+            self._fused_loss = True
+            self._loss_fn = None
+            self._fused = criterion.loss_and_dice
         else:
             # evaluated EAGERLY on the static outputs after the replay: library reductions must not be captured on this
             # stack, exactly as in GraphedStep
@@ -110,7 +117,11 @@ class GraphedEval:
         side = torch.cuda.Stream(device=x.device)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            self._forward(x)
+            warm = self._forward(x)
+            if self._fused_loss and self._fused is not loss_and_dice:
+                with torch.no_grad():      # a RegionLoss keeps its workspace per shape: allocated here, outside the capture
+                    self._fused(warm, t)
+            del warm
             # weight copies registered by that forward leave the pack cache without its pointer tables: build them now
             # (GraphedStep._setup does the same after its dry run), the captured refresh must find them in place
             m._pack_cache.refresh(m.run_dtype)
@@ -125,8 +136,8 @@ class GraphedEval:
         with torch.cuda.graph(g.graph, capture_error_mode=CAPTURE_MODE):
             g.outputs = self._forward(g.x)
             if self._fused_loss:
-                with torch.no_grad():      # no gradient: uz_bce_dice runs with dlogits = NULL
-                    g.loss, g.dice = loss_and_dice(g.outputs, g.t)
+                with torch.no_grad():      # no gradient: uz_bce_dice / uz_region_loss run with dlogits = NULL
+                    g.loss, g.dice = self._fused(g.outputs, g.t)
         _check_capture(g.graph, "evaluation graph")
         g.folded, g.unfolded = self._last_counts
         return g

@@ -148,7 +148,8 @@ class PhasedStep:
         """loss_fn on the outputs of the last emit(); leaves d(loss)/d(output) for backward(..., heads=True)"""
         direct = getattr(self.loss_fn, "direct", None)
         if direct is not None:   # a criterion that hands over its own gradients (the fused BCE + Dice kernel): no autograd node
-            loss, gouts = direct(self.model.wrap_outputs(tuple(o.detach() for o in self._outs)), target)
+            res = direct(self.model.wrap_outputs(tuple(o.detach() for o in self._outs)), target)
+            loss, gouts = res[0], res[-1]   # (loss, gouts), or RegionLoss.direct's (loss, dice, gouts)
             assert len(gouts) == len(self._outs)
             self._gouts = tuple(gouts)
             return loss.detach()

@@ -90,3 +90,204 @@ def loss_and_dice(outputs, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Te
         pairs = [bce_dice_with_logits(v, target) for v in outputs]
         return sum(p[0] for p in pairs), pairs[-1][1]
     return bce_dice_with_logits(outputs, target)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# BCE + region term (soft Dice / Tversky / focal Tversky): uz_region_loss, three launches for any number of output maps
+# ---------------------------------------------------------------------------------------------------------------------
+_REDUCES = ("batch", "image", "channel")
+
+
+def _maps_of(outputs):
+    """(keys or None, the output tensors in the order the model emits them, index of the main output): first value of a
+    dict, last element of a list -- as loss_and_dice picks the map of the Dice metric"""
+    if isinstance(outputs, dict):
+        return tuple(outputs.keys()), tuple(outputs.values()), 0
+    if isinstance(outputs, (list, tuple)):
+        return None, tuple(outputs), len(outputs) - 1
+    return None, (outputs,), 0
+
+
+class _RegionFn(torch.autograd.Function):
+    """ONE node for all output maps: forward is one uz_region_loss call that also writes every map's gradient"""
+
+    @staticmethod
+    def forward(ctx, crit: "RegionLoss", target: torch.Tensor, weights: tuple, main: int, *logits: torch.Tensor):
+        loss, dice, dl = crit._launch(logits, target, weights, main, ctx.needs_input_grad[4:])
+        ctx.dl = dl
+        ctx.in_dtypes = tuple(v.dtype for v in logits)
+        ctx.mark_non_differentiable(dice)
+        return loss, dice
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_dice):
+        return (None, None, None, None) + tuple(None if d is None else (d * g_loss).to(dt)
+                                                for d, dt in zip(ctx.dl, ctx.in_dtypes))
+
+
+class RegionLoss:
+    """``w_bce * BCEWithLogits + w_region * region`` on the device, for every output container of the zoo.
+
+    Per output map (logits ``x`` and target ``t`` of one shape ``(N, K, H, W)``; ``p = sigmoid(x)``)::
+
+        BCE     = mean_i [ -(pos_weight * t_i * log p_i + (1 - t_i) * log(1 - p_i)) ]
+        I_g, S_g, T_g = sum p t, sum p, sum t   over group g of the flattened map
+                  reduce="batch": one group; "image": one per image (K*H*W elements); "channel": one per (image, channel)
+        TI_g    = (I_g + smooth) / (I_g + alpha (S_g - I_g) + beta (T_g - I_g) + smooth)          (Tversky index)
+        region  = mean_g (1 - TI_g) ** gamma                                                      (gamma > 1: focal Tversky)
+        loss    = w_bce * BCE + w_region * region
+
+    ``alpha = beta = 0.5`` is the soft Dice loss: with ``smooth = s / 2`` the index is ``(2 I + s) / (S + T + s)``;
+    ``RegionLoss.dice(smooth=s)`` builds exactly that.  ``alpha`` weighs false positives, ``beta`` false negatives.
+
+    For a dict (u2net) or a list (nested_unet with deep supervision) the loss is ``sum_m output_weights[m] * loss(map_m)``;
+    ``output_weights`` is a sequence in the order the model emits its maps, or a dict by key for dict outputs; the default
+    is one for every map, as in ``loss_and_dice``.
+
+    The Dice METRIC returned beside the loss is ``loss_and_dice``'s: thresholded prediction (``x > 0``), epsilon 1e-7, 1 for
+    an empty union, over the whole MAIN map (first value of a dict, last element of a list).
+
+    One call is one ``uz_region_loss``: three launches whatever the number of maps (two without gradients), fixed summation
+    order, no library reduction -- so ``GraphedStep(model, RegionLoss(...))`` and ``GraphedEval`` keep the loss INSIDE their
+    graphs, where a Python criterion runs eagerly between them.  In a data-parallel step every rank evaluates the loss on its
+    own shard (as the reference's replicas do): ``reduce="batch"`` is therefore per shard, not per global batch.
+
+    The workspace of a (number of maps, shape, device) is kept: calls of one object must follow each other on one stream or
+    be ordered by the caller (``GraphedStep`` / ``GraphedEval`` and plain training loops are).
+    """
+
+    def __init__(self, w_bce: float = 1.0, w_region: float = 1.0, alpha: float = 0.5, beta: float = 0.5,
+                 smooth: float = 1.0, gamma: float = 1.0, reduce: str = "image", pos_weight=None, output_weights=None):
+        def num(name, v):
+            try:
+                f = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"RegionLoss: {name} must be a number, got {v!r}") from None
+            if f != f or f in (float("inf"), float("-inf")):
+                raise ValueError(f"RegionLoss: {name} must be finite, got {v!r}")
+            return f
+        self.w_bce, self.w_region = num("w_bce", w_bce), num("w_region", w_region)
+        self.alpha, self.beta = num("alpha", alpha), num("beta", beta)
+        self.smooth, self.gamma = num("smooth", smooth), num("gamma", gamma)
+        self.pos_weight = 1.0 if pos_weight is None else num("pos_weight", pos_weight)
+        if self.smooth <= 0:
+            raise ValueError(f"RegionLoss: smooth must be > 0, got {smooth!r}")
+        if self.gamma < 1:
+            raise ValueError(f"RegionLoss: gamma must be >= 1, got {gamma!r}")
+        if self.alpha < 0 or self.beta < 0:
+            raise ValueError(f"RegionLoss: alpha and beta must be >= 0, got {alpha!r}, {beta!r}")
+        if self.w_bce < 0 or self.w_region < 0:
+            raise ValueError(f"RegionLoss: w_bce and w_region must be >= 0, got {w_bce!r}, {w_region!r}")
+        if self.w_bce == 0 and self.w_region == 0:
+            raise ValueError("RegionLoss: w_bce and w_region are both zero")
+        if self.pos_weight <= 0:
+            raise ValueError(f"RegionLoss: pos_weight must be > 0, got {pos_weight!r}")
+        if reduce not in _REDUCES:
+            raise ValueError(f"RegionLoss: reduce must be one of {_REDUCES}, got {reduce!r}")
+        self.reduce = reduce
+        if output_weights is None:
+            self.output_weights = None
+        elif isinstance(output_weights, dict):
+            self.output_weights = {k: num(f"output_weights[{k!r}]", v) for k, v in output_weights.items()}
+        else:
+            self.output_weights = tuple(num(f"output_weights[{i}]", v) for i, v in enumerate(output_weights))
+        if self.output_weights is not None:
+            vals = self.output_weights.values() if isinstance(self.output_weights, dict) else self.output_weights
+            if any(v < 0 for v in vals):
+                raise ValueError(f"RegionLoss: output_weights must be >= 0, got {output_weights!r}")
+        self._plans = {}     # (number of maps, shape, device index) -> (descriptor, item table, workspace)
+
+    @classmethod
+    def dice(cls, smooth: float = 1.0, **kw) -> "RegionLoss":
+        """BCE + soft Dice loss ``1 - (2 I + smooth) / (S + T + smooth)``: alpha = beta = 0.5 and half the smoothing"""
+        return cls(alpha=0.5, beta=0.5, smooth=float(smooth) / 2.0, **kw)
+
+    @classmethod
+    def tversky(cls, alpha: float, beta: float, **kw) -> "RegionLoss":
+        """BCE + Tversky loss (``gamma > 1``: focal Tversky); alpha weighs false positives, beta false negatives"""
+        return cls(alpha=alpha, beta=beta, **kw)
+
+    # ------------------------------------------------------------------ the containers
+    def weights_for(self, outputs) -> tuple:
+        """the weight of every output map, in the order the model emits them"""
+        keys, maps, _ = _maps_of(outputs)
+        ow = self.output_weights
+        if ow is None:
+            return (1.0,) * len(maps)
+        if isinstance(ow, dict):
+            if keys is None:
+                raise ValueError("RegionLoss: output_weights is a dict but the outputs are not")
+            missing = [k for k in keys if k not in ow]
+            if missing:
+                raise ValueError(f"RegionLoss: output_weights has no entry for the outputs {missing}")
+            return tuple(ow[k] for k in keys)
+        if len(ow) != len(maps):
+            raise ValueError(f"RegionLoss: {len(ow)} output_weights for {len(maps)} output maps")
+        return ow
+
+    def _groups(self, shape) -> int:
+        if self.reduce == "batch":
+            return 1
+        if len(shape) < 2:
+            raise ValueError(f"RegionLoss: reduce={self.reduce!r} needs (N, K, ...) maps, got shape {tuple(shape)}")
+        return int(shape[0]) if self.reduce == "image" else int(shape[0]) * int(shape[1])
+
+    def _plan(self, n_items: int, shape, device: torch.device, main: int):
+        key = (n_items, tuple(shape), device.index, main)
+        plan = self._plans.get(key)
+        if plan is None:
+            if n_items > L.REGION_MAX_ITEMS:
+                raise ValueError(f"RegionLoss: {n_items} output maps, at most {L.REGION_MAX_ITEMS} per call")
+            n = 1
+            for s in shape:
+                n *= int(s)
+            desc = L.RegionDesc(n_items, n, self._groups(shape), self.w_bce, self.w_region, self.alpha, self.beta,
+                                self.smooth, self.gamma, self.pos_weight, main)
+            ws = torch.empty((L.region_loss_workspace_bytes(desc) + 7) // 8, dtype=torch.float64, device=device)
+            plan = self._plans[key] = (desc, (L.RegionItem * n_items)(), ws)
+        return plan
+
+    def _launch(self, logits, target: torch.Tensor, weights, main: int, need):
+        """one uz_region_loss over all maps -> (loss, dice, [d(loss)/d(map) in fp32, or None where need is False])"""
+        L.require_cuda(target, *logits)
+        for v in logits:
+            if v.shape != target.shape:
+                raise ValueError(f"RegionLoss: an output map of shape {tuple(v.shape)} against a target of shape "
+                                 f"{tuple(target.shape)}")
+            if v.dtype not in (torch.float32, torch.bfloat16):
+                raise ValueError(f"RegionLoss: logits must be float32 or bfloat16, got {v.dtype}")
+            if v.device != target.device:
+                raise ValueError(f"RegionLoss: an output map on {v.device} against a target on {target.device}")
+        if target.numel() == 0:
+            raise ValueError("RegionLoss: empty maps")
+        xs = [v.detach().contiguous().float() for v in logits]     # bf16 logits become fp32, as in bce_dice_with_logits
+        t = target.detach().contiguous().float()
+        desc, items, ws = self._plan(len(xs), t.shape, t.device, main)
+        dl = [torch.empty_like(x) if g else None for x, g in zip(xs, need)]
+        out = torch.empty(2, dtype=torch.float32, device=t.device)
+        for it, x, d, w in zip(items, xs, dl, weights):
+            it.logits, it.target, it.dlogits, it.weight = x.data_ptr(), t.data_ptr(), (d.data_ptr() if d is not None else None), w
+        L.region_loss(desc, items, out, ws)
+        return out[0], out[1], dl
+
+    # ------------------------------------------------------------------ the three forms
+    def loss_and_dice(self, outputs, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(loss, Dice metric of the main output) as 0-dim device tensors; the loss is differentiable with respect to every
+        output tensor through ONE autograd node (any CUDA fp32 / bf16 logits: a stock torch model's too)"""
+        _, maps, main = _maps_of(outputs)
+        return _RegionFn.apply(self, target, self.weights_for(outputs), main, *maps)
+
+    def __call__(self, outputs, target: torch.Tensor) -> torch.Tensor:
+        return self.loss_and_dice(outputs, target)[0]
+
+    def direct(self, outputs, target: torch.Tensor):
+        """(loss, dice, d(loss)/d(outputs)) without an autograd node -- the graphed step's form; the gradients (fp32) come in
+        the order the model emits its outputs (HipModule.wrap_outputs keeps it), as from loss_and_dice_direct"""
+        _, maps, main = _maps_of(outputs)
+        loss, dice, dl = self._launch(maps, target, self.weights_for(outputs), main, (True,) * len(maps))
+        return loss, dice, tuple(dl)
+
+    def __repr__(self) -> str:
+        return (f"RegionLoss(w_bce={self.w_bce}, w_region={self.w_region}, alpha={self.alpha}, beta={self.beta}, "
+                f"smooth={self.smooth}, gamma={self.gamma}, reduce={self.reduce!r}, pos_weight={self.pos_weight}, "
+                f"output_weights={self.output_weights})")

@@ -24,9 +24,11 @@ BASELINE configs[1]).  ``GraphedStep`` is the same step captured once and replay
 them in place, so read (``.item()``) or ``.clone()`` what must outlive the step.
 
 Loss: the default ``criterion="bce_dice"`` is the fused kernel of ``loss.py`` (BCEWithLogits + its gradient + the
-Dice metric, one pass) inside the first graph.  Any callable ``criterion(outputs, target) -> loss`` works too; it is
-evaluated EAGERLY between the forward graph and the backward graphs, because library reductions must not be captured
-on this stack: a memset node of a replayed hipGraph writes its value only in the first replay, and torch's multi-block
+Dice metric, one pass) inside the first graph.  A ``loss.RegionLoss`` instance (BCE + soft Dice / Tversky / focal Tversky,
+weighted over the output maps) sits in the same place: three launches inside the first graph, ``step.dice`` keeps its
+meaning; with several ranks each rank evaluates it on its own shard, so ``reduce="batch"`` is per shard.  Any other
+callable ``criterion(outputs, target) -> loss`` works too; it is evaluated EAGERLY between the forward graph and the
+backward graphs, because library reductions must not be captured on this stack: a memset node of a replayed hipGraph writes its value only in the first replay, and torch's multi-block
 reductions reset their semaphores with exactly such a node (tools/graph_canary.py).
 """
 from __future__ import annotations
@@ -38,7 +40,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from .graph import HipModule, PhasedStep
-from .loss import loss_and_dice, loss_and_dice_direct
+from .loss import RegionLoss, loss_and_dice, loss_and_dice_direct
 from .optim import FlatClipAdamW
 
 # hipGraph capture checks only THIS thread's calls: the process-group watchdog thread polls its events concurrently
@@ -109,7 +111,7 @@ class _ShapeGraphs:
 
 
 class GraphedStep:
-    def __init__(self, model: nn.Module, criterion: Union[str, Callable] = "bce_dice", *, lr: float = 1e-4,
+    def __init__(self, model: nn.Module, criterion: Union[str, RegionLoss, Callable] = "bce_dice", *, lr: float = 1e-4,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-5,
                  max_norm: float = 1.0, phases: int = 5, process_group=None, data_parallel: Optional[bool] = None,
                  cu_reserve: Optional[int] = None, comm: str = "overlap", comm_dtype: Optional[torch.dtype] = None):
@@ -138,6 +140,11 @@ class GraphedStep:
                 raise ValueError(f"unknown built-in criterion {criterion!r}; pass 'bce_dice' or a callable")
             self._fused_loss = True
             self._loss_fn = lambda out, t: loss_and_dice(out, t)[0]
+            self._fused = (loss_and_dice, loss_and_dice_direct)
+        elif isinstance(criterion, RegionLoss):      # fused too: uz_region_loss, graph-safe, hands over its own gradients
+            self._fused_loss = True
+            self._loss_fn = lambda out, t: criterion.loss_and_dice(out, t)[0]
+            self._fused = (criterion.loss_and_dice, criterion.direct)
         else:
             self._fused_loss = False
             self._loss_fn = criterion
@@ -251,14 +258,15 @@ class GraphedStep:
         torch.cuda.synchronize()
         if self._fused_loss:
             dice_box = []
+            with_autograd, direct = self._fused
 
             def fused(out, tt):
-                l, d = loss_and_dice(out, tt)
+                l, d = with_autograd(out, tt)
                 dice_box.append(d)
                 return l
 
             def fused_direct(out, tt):   # the same numbers and d(loss)/d(outputs) without autograd's three extra launches
-                l, d, gouts = loss_and_dice_direct(out, tt)
+                l, d, gouts = direct(out, tt)
                 dice_box.append(d)
                 return l, gouts
             fused.direct = fused_direct
