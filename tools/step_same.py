@@ -1,0 +1,241 @@
+#!/usr/bin/env python3
+"""Does a change of the Python engine leave every launch and every bit where it was?  For a refactor of engine.py / ops.py.
+
+    python tools/step_same.py record OUT.json [--only NAME,...]
+    python tools/step_same.py compare A.json B.json [--log-only NAME,...]
+
+`record` runs each configuration below eagerly under ops.profile_begin() and writes, per configuration, the launch log in
+order (name, flops, bytes of every timed launch; the 1x1 head, which has no timing bracket, is noted by its route) and the
+sha256 of the outputs, the loss, every parameter gradient in named_parameters order and every module buffer after the step.
+Run it with the SAME kernel library in both source trees (UNET_ZOO_AMD_LIB); it uses only API that both trees have.
+`compare` prints one line per configuration and the first difference, exit status 1 on any; --log-only names configurations
+whose numbers differ between two records of ONE tree (compared on their launch log alone, and marked so in the output)."""
+import hashlib
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+# tests/test_step_gpu.py::CASES
+CASES = [
+    ("unet", {}, 2, 64),
+    ("attention_unet", {}, 2, 64),
+    ("u2net", {}, 2, 64),
+    ("swin_unet_v2", {"image_size": 64, "window_size": 4, "drop_path_rate": 0.0}, 2, 64),
+    ("nested_unet", {}, 2, 64),
+    ("resunet", {}, 2, 64),
+    ("missformer", {"image_size": 128}, 2, 128),
+    ("transatt_unet", {}, 2, 64),
+    ("unet_transformer", {}, 2, 64),
+    ("multiresunet", {}, 2, 64),
+    ("uctransnet", {"image_size": 64}, 2, 64),
+]
+EVAL = ("unet", "u2net", "resunet", "vnet", "swin_unet_v2")
+FOLDED = ("unet", "attention_unet", "transatt_unet", "nested_unet")
+OFF = ("fold_bn_apply", "fold_bn_apply_head", "fold_head_grad", "fold_first_bn_bwd", "fuse_bn_reduce", "direct_first_conv")
+SWITCHES = OFF + ("fuse_bn_reduce_convt", "fuse_bn_finalize", "reverse_element_passes", "defer_linear_wgrads", "fold_bn_eval")
+
+
+def _sha(t):
+    return hashlib.sha256(t.detach().contiguous().cpu().view(-1).view(torch.uint8).numpy().tobytes()).hexdigest()
+
+
+def _tensors(o):
+    if isinstance(o, torch.Tensor):
+        return [o]
+    if isinstance(o, dict):
+        return [t for v in o.values() for t in _tensors(v)]
+    return [t for v in o for t in _tensors(v)]
+
+
+def _make(name, kw, dtype):
+    torch.manual_seed(0)
+    if name == "missformer":
+        from unet_zoo_amd.models import MISSFormer
+        m = MISSFormer(num_classes=1, in_channels=3, **kw)
+    else:
+        m = unet_zoo_amd.create_model(name, in_channels=3, num_classes=1, **kw)
+    m.run_dtype = dtype
+    for mod in m.modules():          # dropout off: the records compare kernels, not generator states
+        if isinstance(mod, torch.nn.Dropout):
+            mod.p = 0.0
+    return m.cuda()
+
+
+def _batch(b, size, seed=1):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(b, 3, size, size, generator=g).cuda(), (torch.rand(b, 1, size, size, generator=g) > 0.5).float().cuda())
+
+
+def folds_batch():
+    """the smallest batch at which the 3x3 convolution and its weight gradient read a raw 64-channel 64 x 64 input through
+    BatchNorm + ReLU (host-side plan queries)"""
+    for n in range(1, 65):
+        y = ops.Act(torch.empty((n * 64 * 64, 64), dtype=torch.bfloat16), 0, 64, n, 64, 64)
+        if ops.conv_xform_supported(y, 64, 64) and ops.wgrad_xform_shapes_supported(n, 64, 64, 64, 64, 64, 64, torch.bfloat16):
+            return n
+    raise SystemExit("no batch up to 64 puts a 64 -> 64 channel layer at 64 x 64 on the folded route")
+
+
+def configs(nf):
+    kw = {c[0]: c[1] for c in CASES}
+    out = []
+    for name, k, b, size in CASES:
+        for dt in ("bf16", "fp32"):
+            out.append((f"train/{name}/{dt}", dict(model=name, kw=k, b=b, size=size, dtype=dt, mode="train")))
+    for name in EVAL:
+        for dt in ("bf16", "fp32"):
+            out.append((f"eval/{name}/{dt}", dict(model=name, kw=kw.get(name, {}), b=2, size=64, dtype=dt, mode="eval")))
+    for dt in ("bf16", "fp32"):
+        out.append((f"graphed_eval_fold_bn/unet/{dt}", dict(model="unet", kw={}, b=2, size=64, dtype=dt, mode="graphed_eval")))
+        out.append((f"frozen_backward/unet/{dt}", dict(model="unet", kw={}, b=2, size=64, dtype=dt, mode="frozen")))
+    for name in FOLDED:
+        out.append((f"folds_on/{name}/bf16/N{nf}", dict(model=name, kw={}, b=nf, size=64, dtype="bf16", mode="train")))
+    for s in OFF:
+        out.append((f"switch/{s}=False/unet/bf16/N{nf}", dict(model="unet", kw={}, b=nf, size=64, dtype="bf16", mode="train",
+                                                               switch={s: False})))
+    out.append((f"switch/fuse_bn_finalize=True/unet/bf16/N{nf}", dict(model="unet", kw={}, b=nf, size=64, dtype="bf16", mode="train",
+                                                                     switch={"fuse_bn_finalize": True})))
+    return out
+
+
+def _take_log():
+    log = [[e[0], e[3], e[4]] for e in ops._prof_log]
+    ops._prof_log.clear()       # (the head's notes carry no events: profile_end() must not meet them)
+    ops.profile_end()
+    return log
+
+
+def run(cfg):
+    from unet_zoo_amd.loss import loss_and_dice
+    dtype = torch.bfloat16 if cfg["dtype"] == "bf16" else torch.float32
+    m = _make(cfg["model"], cfg["kw"], dtype)
+    x, t = _batch(cfg["b"], cfg["size"])
+    sha = {}
+    torch.manual_seed(2)
+    if cfg["mode"] == "graphed_eval":
+        ev = unet_zoo_amd.GraphedEval(m.eval(), "bce_dice", fold_bn=True)
+        ops.profile_begin()
+        ev._forward(x)                  # the launches of the captured forward, eagerly (a capture takes no timing events)
+        log = _take_log()
+        loss, dice = ev(x, t)
+        torch.cuda.synchronize()
+        outs = _tensors(ev.outputs)
+        sha["loss"], sha["dice"] = _sha(loss), _sha(dice)
+        sha["layers"] = f"{ev.folded_layers} folded, {ev.unfolded_layers} unfolded"
+    elif cfg["mode"] == "eval":
+        m.eval()
+        ops.profile_begin()
+        with torch.no_grad():
+            outs = _tensors(m(x))
+        log = _take_log()
+    else:
+        m.train() if cfg["mode"] == "train" else m.eval()
+        ops.profile_begin()
+        o = m(x)
+        loss = loss_and_dice(o, t)[0]
+        loss.backward()
+        log = _take_log()
+        outs = _tensors(o)
+        sha["loss"] = _sha(loss)
+        for n, p in m.named_parameters():
+            sha["grad/" + n] = _sha(p.grad) if p.grad is not None else "none"
+    torch.cuda.synchronize()
+    for i, o in enumerate(outs):
+        sha[f"out{i}"] = _sha(o)
+    for n, b in m.named_buffers():
+        sha["buf/" + n] = _sha(b)
+    return log, sha
+
+
+def folded_routes(log):
+    """which of the three folded routes a launch log shows: the 3x3 convolution, its weight gradient, the 1x1 head"""
+    names = [e[0] for e in log]
+    return {"conv_igemm _xf": any(n.endswith("_xf") and not n.startswith("wgrad") for n in names),
+            "wgrad _xf": any(n.endswith("_xf") and n.startswith("wgrad") for n in names),
+            "outconv xform": "outconv_fwd_xf" in names}
+
+
+def record(path, only):
+    defaults = {k: getattr(Engine, k) for k in SWITCHES}
+    fwd, bwd = ops.outconv_fwd, ops.outconv_bwd
+
+    def note(name):
+        if ops._prof_on:
+            ops._prof_log.append((name, None, None, 0.0, 0.0, None))
+
+    def outconv_fwd(x, w, b, xform=None):
+        note("outconv_fwd_xf" if xform is not None else "outconv_fwd")
+        return fwd(x, w, b, xform=xform)
+
+    def outconv_bwd(x, w, g, dx, dw=None, db=None, bnred=None, lazy=False, store_dx=True):
+        note("outconv_bwd" + ("_bnred" if bnred is not None else "") + ("_lazy" if lazy else "") + ("" if store_dx else "_nodx"))
+        return bwd(x, w, g, dx, dw, db, bnred=bnred, lazy=lazy, store_dx=store_dx)
+
+    ops.outconv_fwd, ops.outconv_bwd = outconv_fwd, outconv_bwd
+    nf = folds_batch()
+    res = {"folds_batch": nf, "configs": []}
+    for name, cfg in configs(nf):
+        if only and not any(o in name for o in only):
+            continue
+        for k, v in defaults.items():
+            setattr(Engine, k, v)
+        for k, v in cfg.get("switch", {}).items():
+            setattr(Engine, k, v)
+        log, sha = run(cfg)
+        print(f"{name}: {len(log)} launches", flush=True)
+        if name.startswith("folds_on/unet/"):
+            missing = [k for k, v in folded_routes(log).items() if not v]
+            if missing:
+                raise SystemExit(f"{name} does not cover the folded routes: no {', '.join(missing)} launch")
+        res["configs"].append({"name": name, "log": log, "sha": sha})
+    for k, v in defaults.items():
+        setattr(Engine, k, v)
+    with open(path, "w") as f:
+        json.dump(res, f)
+
+
+def compare(pa, pb, log_only):
+    a, b = json.load(open(pa)), json.load(open(pb))
+    bad = 0
+    print(f"batch of the folded entries: N = {a['folds_batch']}")
+    if a["folds_batch"] != b["folds_batch"] or [c["name"] for c in a["configs"]] != [c["name"] for c in b["configs"]]:
+        print("the two records hold different configurations")
+        return 1
+    for ca, cb in zip(a["configs"], b["configs"]):
+        name, what = ca["name"], None
+        if len(ca["log"]) != len(cb["log"]):
+            what = f"{len(ca['log'])} launches against {len(cb['log'])}"
+        for i, (ea, eb) in enumerate(zip(ca["log"], cb["log"])):
+            if ea != eb:
+                what = f"launch {i}: {ea} against {eb}"
+                break
+        if what is None and name not in log_only:
+            what = next((f"{k}: {ca['sha'].get(k)} against {cb['sha'].get(k)}" for k in list(ca["sha"]) + list(cb["sha"])
+                         if ca["sha"].get(k) != cb["sha"].get(k)), None)
+        routes = ""
+        if name.startswith("folds_on/unet/"):
+            routes = "  [" + ", ".join(k for k, v in folded_routes(ca["log"]).items() if v) + "]"
+        tag = "equal (launch log only)" if name in log_only else "equal"
+        print(f"{name:58s} {len(ca['log']):5d} launches  {tag if what is None else 'DIFFERENT: ' + what}{routes}")
+        bad += what is not None
+    print(f"{len(a['configs']) - bad} of {len(a['configs'])} configurations equal")
+    return 1 if bad else 0
+
+
+def _names(argv, flag):
+    return argv[argv.index(flag) + 1].split(",") if flag in argv else []
+
+
+if __name__ == "__main__":
+    if len(sys.argv) >= 3 and sys.argv[1] == "record":
+        import torch
+        import unet_zoo_amd
+        from unet_zoo_amd import ops
+        from unet_zoo_amd.engine import Engine
+        record(sys.argv[2], _names(sys.argv, "--only"))
+    elif len(sys.argv) >= 4 and sys.argv[1] == "compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3], _names(sys.argv, "--log-only")))
+    else:
+        sys.exit(__doc__)

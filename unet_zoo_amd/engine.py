@@ -11,6 +11,7 @@ momentum and the unbiased variance; eval mode uses the running statistics.
 from __future__ import annotations
 
 import math
+from types import SimpleNamespace
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -23,6 +24,10 @@ from .ops import Act
 
 def _round_up(a: int, b: int) -> int:
     return (a + b - 1) // b * b
+
+
+def _bias_of(m: nn.Module) -> Optional[torch.Tensor]:
+    return m.bias.detach() if m.bias is not None else None
 
 
 class PackCache:
@@ -53,7 +58,9 @@ class PackCache:
         e = self.entries.get(key)
         if e is None:
             if mode == L.PACK_VEC_REPEAT:     # an fp32 vector kpad times over (ConvTranspose2d's bias per sub-pixel)
-                dst = p.detach().float().repeat(kpad).contiguous()
+                # the batched refresh reads p's storage as p.numel() consecutive floats
+                assert p.dtype == torch.float32 and p.is_contiguous(), "PACK_VEC_REPEAT takes a contiguous fp32 vector"
+                dst = p.detach().repeat(kpad).contiguous()
             else:
                 dst = ops.pack_weights(p.detach(), mode, dtype, kpad)   # packed now, batched from the next step on
             self.entries[key] = (p, mode, kpad, dtype, dst)
@@ -103,6 +110,7 @@ class PackCache:
         begin = 0
         for i, (p, mode, kpad, dst) in enumerate(generic):
             if mode == L.PACK_VEC_REPEAT:
+                assert dst.dtype == torch.float32
                 arr[i] = L.PackItem(p.data_ptr(), dst.data_ptr(), begin, mode, p.numel(), 1, kpad, 0, 0)
                 begin += dst.numel()
                 continue
@@ -387,191 +395,213 @@ class Engine:
         weight gradient can read the raw output through BatchNorm + ReLU (Engine.fold_bn_apply), the apply pass is not run
         and the returned activation is LAZY (Act.lazy = (scale, shift) over the raw buffer); the caller hands it to
         conv_bn_relu(..., sole_reader=True) and to nothing else.  Returns (act, pooled)."""
-        N, H, W = x.N, x.H, x.W
-        if upsample:
-            H, W = 2 * H, 2 * W
-        tmode = L.TAPS_CONV_UP2 if upsample else L.TAPS_CONV
-        Cout = conv.out_channels
-        xf = getattr(x, "lazy", None)      # x is the raw output of a convolution, to be read through its BatchNorm + ReLU
-        assert xf is None or (sole_reader and not im2col and conv.kernel_size == (3, 3) and conv.dilation == (1, 1)), \
+        assert not (isinstance(x, Act) and x.lazy is not None) \
+            or (sole_reader and not im2col and conv.kernel_size == (3, 3) and conv.dilation == (1, 1)), \
             "a lazy activation goes to the 3x3 convolution it was deferred for"
-        dil = conv.dilation[0]
-        image = None       # the fp32 NCHW input when the direct first-convolution kernels take this layer
-        if im2col and isinstance(x, ImageInput):
-            if (self.direct_first_conv and conv.kernel_size == (3, 3) and dil == 1 and conv.padding == (1, 1)
-                    and conv.stride == (1, 1) and ops.conv_first_supported(self.dtype, x.nchw.shape[1], Cout)):
-                image = x.nchw
-                # the backward's weight gradient reads the caller's OWN tensor (contiguous fp32 input: no copy was made): an
-                # in-place change of the input between forward and backward is caught there instead of giving a wrong dW
-                image_version = image._version
-            else:
-                x = x.patches()
-        if image is not None:
-            wp, ntaps = None, 1
-        elif im2col:
-            wp = self._pack(conv.weight, L.PACK_IM2COL, x.C)
-            ntaps = 1
-        else:
-            assert conv.kernel_size in ((3, 3), (1, 1)) and conv.in_channels == x.C
-            wp = self._pack(conv.weight, L.PACK_CONV_FWD)
-            ntaps = 9 if conv.kernel_size == (3, 3) else 1     # 1x1 + BN + ReLU: unet_transformer.py:150-177
-            assert ntaps == 9 or not upsample
+        xf = x.take_lazy() if isinstance(x, Act) else None   # x is the raw output of a convolution: read through this map
+        N, H, W = (x.N, 2 * x.H, 2 * x.W) if upsample else (x.N, x.H, x.W)
+        x, image, image_version, wp, ntaps, tmode, dil = self._lower_conv(x, conv, im2col, upsample)
+        bare = not pool and residual is None and stat_repeat == 1      # nothing but BatchNorm [+ ReLU] behind the convolution
         if self.fold_bn_eval and not self.training and not self.record:
             act = self._conv_bn_relu_folded(x, conv, bn, out, image, wp, ntaps, dil, tmode, relu, N, H, W) \
-                if (not pool and residual is None and stat_repeat == 1 and xf is None) else None
+                if (bare and xf is None) else None
             if act is not None:
                 self.folded_layers += 1
                 return act, None
             self.unfolded_layers += 1
-        y = self.new_act(N, H, W, Cout)
-        bias = conv.bias.detach() if conv.bias is not None else None
+        y = self.new_act(N, H, W, conv.out_channels)
         if image is not None:
-            stats = ops.conv_first_fwd(image, conv.weight.detach(), bias, y, self.training)
+            stats = ops.conv_first_fwd(image, conv.weight.detach(), _bias_of(conv), y, self.training)
         else:
-            stats = ops.conv_igemm(x, wp, bias, y, ntaps=ntaps, dil=dil, taps_mode=tmode,
+            stats = ops.conv_igemm(x, wp, _bias_of(conv), y, ntaps=ntaps, dil=dil, taps_mode=tmode,
                                    want_stats=self.training, xform=xf)
-        lazy = False
-        if (defer_apply is not None and self.fold_bn_apply and out is None and not pool and residual is None and relu
-                and stat_repeat == 1 and self.dtype == torch.bfloat16 and defer_apply.kernel_size == (3, 3)
-                and defer_apply.dilation == (1, 1) and defer_apply.stride == (1, 1) and defer_apply.in_channels == Cout):
-            # both kernels of the reader must take the map (the weight gradient's L operand has the reader's channels)
-            c2 = defer_apply.out_channels
-            lazy = (ops.conv_xform_supported(y, c2, c2)
-                    and ops.wgrad_xform_shapes_supported(N, H, W, c2, c2, Cout, y.ld, self.dtype))
-        elif (defer_apply is not None and self.fold_bn_apply and self.fold_bn_apply_head and out is None and not pool
-                and residual is None and relu and stat_repeat == 1 and defer_apply.kernel_size == (1, 1)
-                and defer_apply.in_channels == Cout and (self.training or not self.record)):
-            # the reader is the 1x1 head (out_conv): its forward reads the raw tensor through the map, its backward takes the
-            # gradient AND this BatchNorm's first backward pass from the raw tensor alone (uz_outconv_bwd_bnred, x = NULL) --
-            # which needs batch statistics on the tape (training), or no tape at all
-            lazy = self.fuse_bn_reduce_convt and ops.outconv_xform_supported(y, defer_apply.out_channels)
+        lazy = (defer_apply is not None and bare and relu and out is None
+                and (self._defer_to_conv3x3(y, defer_apply) or self._defer_to_head(y, defer_apply)))
         # the finalize inside the apply pass's launch: training statistics, an apply pass to ride in
         fin = self._fin_flag() if (self.training and not lazy and stat_repeat == 1) else None
-        vec = None
-        if self.training:
-            mom = bn.momentum if bn.momentum is not None else 0.1
-            if fin is None:
-                vec = ops.bn_finalize(stats if stat_repeat == 1 else stats * float(stat_repeat), y.P * stat_repeat,
-                                      bn.weight.detach(), bn.bias.detach(), bn.eps, mom, bn.running_mean, bn.running_var)
-            if bn.num_batches_tracked is not None:
-                self._bn_counters.append(bn.num_batches_tracked)   # bumped together in finish_forward()
-        else:
-            vec = self._bn_vectors(bn, None, y.P)      # running statistics: (scale, shift, mean, invstd)
+        vec = self._bn_vectors(bn, stats, y.P, stat_repeat) if fin is None else None
         if lazy:
-            act = ops.Act(y.buf, y.off, y.C, N, H, W, True)
+            act, pooled = ops.Act(y.buf, y.off, y.C, N, H, W, True), None
             act.lazy = (vec[0], vec[1])
-            pooled = None
         else:
-            act = out if out is not None else self.new_act(N, H, W, Cout)
-            if pool and pool_ceil:
-                pooled = self.new_act(N, (H + 1) // 2, (W + 1) // 2, Cout)
-            else:
-                pooled = self.new_act(N, H // 2, W // 2, Cout) if pool else None
-            assert relu or residual is None
-            if fin is not None:
-                vec = ops.bn_relu_apply_fin(y, stats, y.P, bn.weight.detach(), bn.bias.detach(), bn.eps, mom, bn.running_mean,
-                                            bn.running_var, fin, act, pooled, residual, pool_ceil, relu=relu)
-            else:
-                ops.bn_relu_apply(y, vec[0], vec[1], act, pooled, residual, pool_ceil, relu=relu,
-                                  reverse=self.reverse_element_passes)
+            act, pooled, vec = self._bn_relu_apply(y, bn, vec, stats, fin, out, pool, pool_ceil, residual, relu)
         if self.record and self.training and relu and pooled is None and residual is None and stat_repeat == 1:
             act.bn_src = (y, vec)      # what a sole reader's input-gradient kernel needs (see sole_reader)
-
-        frozen = not self.training     # model.eval() + backward(): BatchNorm is an affine map of constants
         if self.record:
-            self._bn_channels += Cout
+            self._bn_channels += y.C
+            # what the backward needs, the forward's routes included (frozen: model.eval() + backward(), BatchNorm is affine)
+            lay = SimpleNamespace(x=x, conv=conv, bn=bn, y=y, vec=vec, act=act, pooled=pooled, residual=residual, relu=relu,
+                                  pool_ceil=pool_ceil, frozen=not self.training, image=image, image_version=image_version,
+                                  im2col=im2col, upsample=upsample, ntaps=ntaps, tmode=tmode, dil=dil, xf=xf,
+                                  sole_reader=sole_reader)
 
-            def bwd():
-                gs = self._sum_grads(act, 2)
-                gp = self._sum_grads(pooled, 1)[0] if (pooled is not None and pooled.grads) else None
-                g0 = gs[0] if len(gs) > 0 else None
-                g1 = gs[1] if len(gs) > 1 else None
-                if g0 is None and gp is None:
-                    return  # nothing downstream used this activation
-                head = isinstance(g0, ops.HeadGrad)   # the 1x1 head wrote no gradient (fold_head_grad): the apply pass forms it
-                assert not head or (g1 is None and gp is None and residual is None and relu and not frozen and pooled is None)
-                if residual is not None:
-                    # the residual branch needs the TOTAL gradient of act as one tensor; the pool's
-                    # argmax is over act (= relu + residual), not over relu(bn(y))
-                    if gp is not None or g1 is not None:
-                        tot = self.new_act(N, H, W, Cout)
-                        ops.pool_grad_combine(act, g0, g1, gp, tot, pool_ceil)
-                        g0, g1, gp = tot, None, None
-                    if residual.needs_grad:
-                        residual.add_grad(g0)
-                # the first layer: the weight gradient is dy's only reader and forms it itself (uz_conv3x3_first_wgrad_bn); only
-                # the reduction and its finalize (dgamma, dbeta, the totals) run here and no dy exists
-                fold_first = (self.fold_first_bn_bwd and image is not None and not frozen and relu and not head
-                              and self.dtype == torch.bfloat16 and pooled is None and residual is None and g1 is None
-                              and gp is None and not self.fuse_bn_finalize)
-                dy = None if fold_first else self.new_act(N, H, W, Cout)
-                dgamma, dbeta = self._dst(bn.weight), self._dst(bn.bias)
-                if dgamma is None:
-                    dgamma = torch.empty(Cout, dtype=torch.float32, device=self.device)
-                if dbeta is None:
-                    dbeta = torch.empty(Cout, dtype=torch.float32, device=self.device)
-                sums = self._bn_sums(Cout)
-                if head:
-                    ops.bn_relu_bwd_head(y, vec, g0, sums, dy, dgamma, dbeta, reverse=self.reverse_element_passes)
-                else:
-                    # g0 came from a sole reader's input-gradient kernel with the reduction already done in its epilogue
-                    parts = getattr(g0, "bn_partials", None) if (g1 is None and gp is None and residual is None) else None
-                    ops.bn_relu_bwd(y, vec, g0, g1, gp, sums, dy, dgamma, dbeta, pool_ceil, relu=relu,
-                                    partials=parts, frozen=frozen, fin_flag=None if frozen else self._fin_flag(),
-                                    reverse=self.reverse_element_passes)
-                self._give_grad(bn.weight, dgamma)
-                self._give_grad(bn.bias, dbeta)
-                if conv.bias is not None:
-                    if frozen:
-                        self._bias_grad(conv.bias, dy)     # running statistics do not cancel a per-channel constant
-                    else:
-                        # d(bias) = sum_p dy == 0 analytically under train-mode BN (the batch mean
-                        # removes any per-channel constant); the reference's value is rounding noise.
-                        self._give_grad(conv.bias, None)
-                if image is not None:
-                    if image._version != image_version:
-                        raise RuntimeError("the network input was modified in place between forward and backward: the first "
-                                           "convolution's weight gradient reads it (pass a copy, or finish backward first)")
-                    if fold_first:
-                        self._give_grad(conv.weight, ops.conv_first_wgrad_bn(image, g0, y, vec, sums, out=self._dst(conv.weight)))
-                    else:
-                        self._give_grad(conv.weight, ops.conv_first_wgrad(image, dy, out=self._dst(conv.weight)))
-                elif im2col:
-                    dwp = ops.wgrad(dy, x, (Cout, x.C), ntaps=1)
-                    cin = conv.in_channels
-                    dw = dwp[:, :9 * cin].reshape(Cout, 9, cin).permute(0, 2, 1).reshape(conv.weight.shape)
-                    self._give_grad(conv.weight, dw.contiguous())
-                else:
-                    if ntaps == 1 and tmode == L.TAPS_CONV:
-                        self._linear_wgrad(conv.weight, dy, x)      # a 1x1 convolution is a Linear layer on the pixel list
-                    else:
-                        self._give_grad(conv.weight, ops.wgrad(dy, x, tuple(conv.weight.shape), ntaps=ntaps,
-                                                               dil=dil, taps_mode=tmode,
-                                                               out=self._dst(conv.weight), xform=xf))
-                    if x.needs_grad and upsample:
-                        # gradient of the (virtual) upsampled tensor, then 2x2 sums
-                        du = self.new_act(N, H, W, x.C)
-                        ops.conv_igemm(dy, self._pack(conv.weight, L.PACK_CONV_DGRAD), None, du,
-                                       ntaps=9, dil=dil)
-                        dx = self.new_act(x.N, x.H, x.W, x.C)
-                        ops.sum2x2(du, dx)
-                        x.add_grad(dx)
-                    elif x.needs_grad:
-                        dx = self.new_act(N, H, W, x.C)
-                        # per-channel sums of dx come for free from the kernel's statistics
-                        # epilogue; a ConvTranspose2d feeding x takes its bias gradient from them
-                        want = x.parts is not None
-                        src = getattr(x, "bn_src", None) if (sole_reader and not want and self.fuse_bn_reduce) else None
-                        part = ops.conv_igemm(dy, self._pack(conv.weight, L.PACK_CONV_DGRAD), None, dx,
-                                              ntaps=ntaps, dil=dil, want_stats=want, bnred=src)
-                        if want:
-                            dx.colsums = (part, 0)
-                        elif src is not None and part is not None:
-                            dx.bn_partials = part
-                        x.add_grad(dx)
+            def bwd():      # ONE tape entry: BatchNorm + ReLU backward, then the convolution's weight and input gradients
+                r = self._conv_bn_relu_bwd_bn(lay)
+                if r is not None:       # (else nothing downstream used this activation)
+                    self._conv_bn_relu_bwd_conv(lay, *r)
 
             self.tape.append(bwd)
         return act, pooled
+
+    def _lower_conv(self, x, conv: nn.Conv2d, im2col: bool, upsample: bool):
+        """How conv_bn_relu runs its convolution: (x, image, image_version, wp, ntaps, tmode, dil).  image = the fp32 NCHW input
+        where the direct first-convolution kernels take the layer; else x is an Act (im2col: the patches), wp its packed weights"""
+        dil = conv.dilation[0]
+        tmode = L.TAPS_CONV_UP2 if upsample else L.TAPS_CONV
+        if im2col and isinstance(x, ImageInput):
+            if (self.direct_first_conv and conv.kernel_size == (3, 3) and dil == 1 and conv.padding == (1, 1)
+                    and conv.stride == (1, 1) and ops.conv_first_supported(self.dtype, x.nchw.shape[1], conv.out_channels)):
+                # the backward's weight gradient reads the caller's OWN tensor (contiguous fp32 input: no copy was made): an
+                # in-place change of the input between forward and backward is caught there instead of giving a wrong dW
+                return x, x.nchw, x.nchw._version, None, 1, tmode, dil
+            x = x.patches()
+        if im2col:
+            return x, None, None, self._pack(conv.weight, L.PACK_IM2COL, x.C), 1, tmode, dil
+        assert conv.kernel_size in ((3, 3), (1, 1)) and conv.in_channels == x.C
+        ntaps = 9 if conv.kernel_size == (3, 3) else 1     # 1x1 + BN + ReLU: unet_transformer.py:150-177
+        assert ntaps == 9 or not upsample
+        return x, None, None, self._pack(conv.weight, L.PACK_CONV_FWD), ntaps, tmode, dil
+
+    def _defer_to_conv3x3(self, y: Act, reader: nn.Conv2d) -> bool:
+        """may the apply pass behind the raw output y be left out for its one reader, a 3x3 convolution?  Both kernels of the
+        reader must take the map (the weight gradient's L operand has the reader's channels)"""
+        c2 = reader.out_channels
+        return (self.fold_bn_apply and self.dtype == torch.bfloat16 and reader.kernel_size == (3, 3)
+                and reader.dilation == (1, 1) and reader.stride == (1, 1) and reader.in_channels == y.C
+                and ops.conv_xform_supported(y, c2, c2)
+                and ops.wgrad_xform_shapes_supported(y.N, y.H, y.W, c2, c2, y.C, y.ld, self.dtype))
+
+    def _defer_to_head(self, y: Act, reader: nn.Conv2d) -> bool:
+        """... for the 1x1 head (out_conv)?  Its forward reads the raw tensor through the map, its backward takes the gradient AND this
+        BatchNorm's first pass from the raw tensor alone (uz_outconv_bwd_bnred, x = NULL): batch statistics on the tape, or no tape"""
+        return (self.fold_bn_apply and self.fold_bn_apply_head and reader.kernel_size == (1, 1) and reader.in_channels == y.C
+                and (self.training or not self.record) and self.fuse_bn_reduce_convt
+                and ops.outconv_xform_supported(y, reader.out_channels))
+
+    def _bn_relu_apply(self, y: Act, bn, vec, stats, fin, out, pool: bool, pool_ceil: bool, residual, relu: bool):
+        """conv_bn_relu's apply pass [+ residual, + pool] over the raw output y; fin: the flag of a finalize that rides in the
+        same launch (vec is then made here).  Returns (act, pooled, vec)."""
+        act = out if out is not None else self.new_act(y.N, y.H, y.W, y.C)
+        ph, pw = ((y.H + 1) // 2, (y.W + 1) // 2) if pool_ceil else (y.H // 2, y.W // 2)
+        pooled = self.new_act(y.N, ph, pw, y.C) if pool else None
+        assert relu or residual is None
+        if fin is not None:
+            vec = ops.bn_relu_apply_fin(y, stats, y.P, bn.weight.detach(), bn.bias.detach(), bn.eps, self._momentum(bn),
+                                        bn.running_mean, bn.running_var, fin, act, pooled, residual, pool_ceil, relu=relu)
+        else:
+            ops.bn_relu_apply(y, vec[0], vec[1], act, pooled, residual, pool_ceil, relu=relu,
+                              reverse=self.reverse_element_passes)
+        return act, pooled, vec
+
+    def _conv_bn_relu_bwd_bn(self, s):
+        """Gives the BatchNorm's and the convolution bias's gradients; returns (dy, g0, sums): the gradient of the raw output
+        -- or dy = None where its one reader, the first layer's weight gradient, forms it itself from g0 and the totals."""
+        y, bn, residual, act, pooled = s.y, s.bn, s.residual, s.act, s.pooled
+        gs = self._sum_grads(act, 2)
+        gp = self._sum_grads(pooled, 1)[0] if (pooled is not None and pooled.grads) else None
+        g0, g1 = (gs + [None, None])[:2]
+        if g0 is None and gp is None:
+            return None
+        head = isinstance(g0, ops.HeadGrad)   # the 1x1 head wrote no gradient (fold_head_grad): the apply pass forms it
+        assert not head or (g1 is None and gp is None and residual is None and s.relu and not s.frozen and pooled is None)
+        if residual is not None:
+            # the residual branch needs the TOTAL gradient of act as one tensor; the pool's
+            # argmax is over act (= relu + residual), not over relu(bn(y))
+            if gp is not None or g1 is not None:
+                tot = self.new_act(y.N, y.H, y.W, y.C)
+                ops.pool_grad_combine(act, g0, g1, gp, tot, s.pool_ceil)
+                g0, g1, gp = tot, None, None
+            if residual.needs_grad:
+                residual.add_grad(g0)
+        # the first layer: the weight gradient is dy's only reader and forms it itself (uz_conv3x3_first_wgrad_bn); only
+        # the reduction and its finalize (dgamma, dbeta, the totals) run here and no dy exists
+        fold_first = (self.fold_first_bn_bwd and s.image is not None and not s.frozen and s.relu and not head
+                      and self.dtype == torch.bfloat16 and pooled is None and residual is None and g1 is None
+                      and gp is None and not self.fuse_bn_finalize)
+        dy = None if fold_first else self.new_act(y.N, y.H, y.W, y.C)
+        dgamma, dbeta = self._bn_grad_dst(bn, y.C)
+        sums = self._bn_sums(y.C)
+        if head:
+            ops.bn_relu_bwd_head(y, s.vec, g0, sums, dy, dgamma, dbeta, reverse=self.reverse_element_passes)
+        else:
+            # g0 came from a sole reader's input-gradient kernel with the reduction already done in its epilogue
+            parts = g0.bn_partials if (g1 is None and gp is None and residual is None) else None
+            ops.bn_relu_bwd(y, s.vec, g0, g1, gp, sums, dy, dgamma, dbeta, s.pool_ceil, relu=s.relu,
+                            partials=parts, frozen=s.frozen, fin_flag=None if s.frozen else self._fin_flag(),
+                            reverse=self.reverse_element_passes)
+        self._give_grad(bn.weight, dgamma)
+        self._give_grad(bn.bias, dbeta)
+        if s.conv.bias is not None:
+            if s.frozen:
+                self._bias_grad(s.conv.bias, dy)     # running statistics do not cancel a per-channel constant
+            else:
+                # d(bias) = sum_p dy == 0 analytically under train-mode BN (the batch mean
+                # removes any per-channel constant); the reference's value is rounding noise.
+                self._give_grad(s.conv.bias, None)
+        return dy, g0, sums
+
+    def _conv_bn_relu_bwd_conv(self, s, dy: Optional[Act], g0, sums: torch.Tensor) -> None:
+        """the convolution's weight gradient, then its input gradient, from the gradient dy of its raw output"""
+        conv, x, y = s.conv, s.x, s.y
+        if s.image is not None:
+            if s.image._version != s.image_version:
+                raise RuntimeError("the network input was modified in place between forward and backward: the first "
+                                   "convolution's weight gradient reads it (pass a copy, or finish backward first)")
+            dst = self._dst(conv.weight)
+            self._give_grad(conv.weight, ops.conv_first_wgrad_bn(s.image, g0, y, s.vec, sums, out=dst) if dy is None
+                            else ops.conv_first_wgrad(s.image, dy, out=dst))
+            return
+        if s.im2col:
+            self._im2col_wgrad(conv, dy, x)
+            return
+        self._conv_wgrad(conv, dy, x, s.ntaps, s.dil, s.tmode, s.xf)
+        if x.needs_grad and s.upsample:
+            # gradient of the (virtual) upsampled tensor, then 2x2 sums
+            du, _ = self._conv_dgrad(conv, dy, 9, s.dil)
+            dx = self.new_act(x.N, x.H, x.W, x.C)
+            ops.sum2x2(du, dx)
+            x.add_grad(dx)
+        elif x.needs_grad:
+            # per-channel sums of dx come for free from the kernel's statistics
+            # epilogue; a ConvTranspose2d feeding x takes its bias gradient from them
+            want = x.parts is not None
+            src = x.bn_src if (s.sole_reader and not want and self.fuse_bn_reduce) else None
+            dx, part = self._conv_dgrad(conv, dy, s.ntaps, s.dil, want_stats=want, bnred=src)
+            if want:
+                dx.colsums = (part, 0)
+            elif src is not None and part is not None:
+                dx.bn_partials = part
+            x.add_grad(dx)
+
+    # ---- pieces shared by the convolution blocks' backward passes
+    def _bn_grad_dst(self, bn, C: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """where a BatchNorm's (dgamma, dbeta) go: the parameters' .grad in in-place mode, else fresh vectors"""
+        dsts = self._dst(bn.weight), self._dst(bn.bias)
+        return tuple(d if d is not None else torch.empty(C, dtype=torch.float32, device=self.device) for d in dsts)
+
+    def _momentum(self, bn, count: bool = True) -> float:
+        """a train-mode BatchNorm's momentum; count: its num_batches_tracked is bumped with the others in finish_forward()"""
+        if count and bn.num_batches_tracked is not None:
+            self._bn_counters.append(bn.num_batches_tracked)
+        return bn.momentum if bn.momentum is not None else 0.1
+
+    def _im2col_wgrad(self, conv: nn.Conv2d, g: Act, patches: Act) -> None:
+        """weight gradient of a convolution run as a GEMM on k x k patches [P][Kpad]: the one-tap product, back in (Co, Ci, k, k)"""
+        co, ci, T = conv.out_channels, conv.in_channels, conv.kernel_size[0] * conv.kernel_size[1]
+        dwp = ops.wgrad(g, patches, (co, patches.C), ntaps=1)
+        self._give_grad(conv.weight, dwp[:, :T * ci].reshape(co, T, ci).permute(0, 2, 1).reshape(conv.weight.shape).contiguous())
+
+    def _conv_wgrad(self, conv: nn.Conv2d, g: Act, x: Act, ntaps: int, dil: int = 1, tmode: int = L.TAPS_CONV, xform=None) -> None:
+        if ntaps == 1 and tmode == L.TAPS_CONV:
+            self._linear_wgrad(conv.weight, g, x)      # a 1x1 convolution is a Linear layer on the pixel list
+        else:
+            self._give_grad(conv.weight, ops.wgrad(g, x, tuple(conv.weight.shape), ntaps=ntaps, dil=dil, taps_mode=tmode,
+                                                   out=self._dst(conv.weight), xform=xform))
+
+    def _conv_dgrad(self, conv: nn.Conv2d, g: Act, ntaps: int, dil: int = 1, **kw):
+        """(dx, what conv_igemm returned): the stride-1 input-gradient convolution of g through PACK_CONV_DGRAD weights"""
+        dx = self.new_act(g.N, g.H, g.W, conv.in_channels)
+        return dx, ops.conv_igemm(g, self._pack(conv.weight, L.PACK_CONV_DGRAD), None, dx, ntaps=ntaps, dil=dil, **kw)
 
     def _conv_bn_relu_folded(self, x, conv: nn.Conv2d, bn: nn.BatchNorm2d, out: Optional[Act], image, wp, ntaps: int,
                              dil: int, tmode: int, relu: bool, N: int, H: int, W: int) -> Optional[Act]:
@@ -586,11 +616,10 @@ class Engine:
             return None
         v2 = ops.bn_eval_scale(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps)
         act = out if out is not None else self.new_act(N, H, W, Cout)
-        bias = conv.bias.detach() if conv.bias is not None else None
         if image is not None:
-            ops.conv_first_fwd_bnact(image, conv.weight.detach(), bias, v2[0], v2[1], relu, act)
+            ops.conv_first_fwd_bnact(image, conv.weight.detach(), _bias_of(conv), v2[0], v2[1], relu, act)
         else:
-            ops.conv_igemm_bnact(x, wp, bias, v2[0], v2[1], relu, act, ntaps=ntaps, dil=dil, taps_mode=tmode)
+            ops.conv_igemm_bnact(x, wp, _bias_of(conv), v2[0], v2[1], relu, act, ntaps=ntaps, dil=dil, taps_mode=tmode)
         return act
 
     def attention_gate(self, g: Act, x: Act, blk: nn.Module, out: Act) -> Act:
@@ -605,16 +634,14 @@ class Engine:
 
         def conv1x1_bn(src: Act, conv: nn.Conv2d, bn: nn.BatchNorm2d):
             raw = self.new_act(N, H, W, conv.out_channels)
-            st = ops.conv_igemm(src, self._pack(conv.weight, L.PACK_CONV_FWD),
-                                conv.bias.detach() if conv.bias is not None else None, raw, ntaps=1,
+            st = ops.conv_igemm(src, self._pack(conv.weight, L.PACK_CONV_FWD), _bias_of(conv), raw, ntaps=1,
                                 want_stats=self.training)
             return raw, self._bn_vectors(bn, st, P)
 
         g1, vec_g = conv1x1_bn(g, conv_g, bn_g)
         x1, vec_x = conv1x1_bn(x, conv_x, bn_x)
         wpsi = conv_q.weight.detach().reshape(Fi)
-        q, part = ops.attn_psi_fwd(g1, x1, vec_g, vec_x, wpsi,
-                                   conv_q.bias.detach() if conv_q.bias is not None else None)
+        q, part = ops.attn_psi_fwd(g1, x1, vec_g, vec_x, wpsi, _bias_of(conv_q))
         vec_q = self._bn_vectors(bn_q, part, P)
         ops.attn_gate_fwd(x, q, vec_q, out)
 
@@ -652,28 +679,20 @@ class Engine:
                 self._linear_wgrad(conv_g.weight, dg1, g)      # 1x1 convolutions: with the deferred set (uz_wgrad_multi)
                 self._linear_wgrad(conv_x.weight, dx1, x)
                 if g.needs_grad:
-                    dg = self.new_act(N, H, W, g.C)
-                    ops.conv_igemm(dg1, self._pack(conv_g.weight, L.PACK_CONV_DGRAD), None, dg, ntaps=1)
-                    g.add_grad(dg)
+                    g.add_grad(self._conv_dgrad(conv_g, dg1, 1)[0])
                 if x.needs_grad:
-                    dxx = self.new_act(N, H, W, x.C)
-                    ops.conv_igemm(dx1, self._pack(conv_x.weight, L.PACK_CONV_DGRAD), None, dxx, ntaps=1)
-                    x.add_grad(dxx)
+                    x.add_grad(self._conv_dgrad(conv_x, dx1, 1)[0])
                     x.add_grad(dxd)
 
             self.tape.append(bwd)
         return out
 
-    def _bn_vectors(self, bn: nn.BatchNorm2d, stats: Optional[torch.Tensor], count: int) -> torch.Tensor:
+    def _bn_vectors(self, bn: nn.BatchNorm2d, stats: Optional[torch.Tensor], count: int, repeat: int = 1) -> torch.Tensor:
         """(scale, shift, mean, invstd) rows for a BatchNorm: batch statistics + running-stat update
-        in training, running statistics in eval."""
+        in training, running statistics in eval.  repeat: conv_bn_relu's stat_repeat."""
         if self.training:
-            mom = bn.momentum if bn.momentum is not None else 0.1
-            vec = ops.bn_finalize(stats, count, bn.weight.detach(), bn.bias.detach(), bn.eps, mom,
-                                  bn.running_mean, bn.running_var)
-            if bn.num_batches_tracked is not None:
-                self._bn_counters.append(bn.num_batches_tracked)   # bumped together in finish_forward()
-            return vec
+            return ops.bn_finalize(stats if repeat == 1 else stats * float(repeat), count * repeat, bn.weight.detach(),
+                                   bn.bias.detach(), bn.eps, self._momentum(bn), bn.running_mean, bn.running_var)
         v2 = ops.bn_eval_scale(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps)
         return torch.cat([v2, bn.running_mean.reshape(1, -1), torch.rsqrt(bn.running_var + bn.eps).reshape(1, -1)])
 
@@ -699,11 +718,7 @@ class Engine:
                 if not gs and gp is None:
                     return
                 dx = self.new_act(x.N, x.H, x.W, C)
-                dgamma, dbeta = self._dst(bn.weight), self._dst(bn.bias)
-                if dgamma is None:
-                    dgamma = torch.empty(C, dtype=torch.float32, device=self.device)
-                if dbeta is None:
-                    dbeta = torch.empty(C, dtype=torch.float32, device=self.device)
+                dgamma, dbeta = self._bn_grad_dst(bn, C)
                 ops.bn_relu_bwd(x, vec, gs[0] if gs else None, gs[1] if len(gs) > 1 else None, gp, self._bn_sums(C), dx,
                                 dgamma, dbeta, relu=relu, frozen=frozen)
                 self._give_grad(bn.weight, dgamma)
@@ -730,7 +745,7 @@ class Engine:
             assert conv.in_channels == x.C
             wp, ntaps = self._pack(conv.weight, L.PACK_CONV_FWD), k * k
         y = self.new_act(x.N, x.H, x.W, Cout)
-        ops.conv_igemm(x, wp, conv.bias.detach() if conv.bias is not None else None, y, ntaps=ntaps, res=residual)
+        ops.conv_igemm(x, wp, _bias_of(conv), y, ntaps=ntaps, res=residual)
         if self.record:
             def bwd():
                 g = self._total_grad(y)
@@ -741,20 +756,11 @@ class Engine:
                 if conv.bias is not None:
                     self._bias_grad(conv.bias, g)
                 if im2col:
-                    dwp = ops.wgrad(g, x, (Cout, x.C), ntaps=1)
-                    cin = conv.in_channels
-                    dw = dwp[:, :9 * cin].reshape(Cout, 9, cin).permute(0, 2, 1).reshape(conv.weight.shape)
-                    self._give_grad(conv.weight, dw.contiguous())
+                    self._im2col_wgrad(conv, g, x)
                     return
-                if ntaps == 1:
-                    self._linear_wgrad(conv.weight, g, x)
-                else:
-                    self._give_grad(conv.weight, ops.wgrad(g, x, tuple(conv.weight.shape), ntaps=ntaps,
-                                                           out=self._dst(conv.weight)))
+                self._conv_wgrad(conv, g, x, ntaps)
                 if x.needs_grad:
-                    dx = self.new_act(x.N, x.H, x.W, x.C)
-                    ops.conv_igemm(g, self._pack(conv.weight, L.PACK_CONV_DGRAD), None, dx, ntaps=ntaps)
-                    x.add_grad(dx)
+                    x.add_grad(self._conv_dgrad(conv, g, ntaps)[0])
 
             self.tape.append(bwd)
         return y
@@ -769,8 +775,7 @@ class Engine:
         N, H, W, Cout = x.N, x.H, x.W, conv.out_channels
         Ho, Wo = (H + 1) // 2, (W + 1) // 2
         y = self.new_act(N, Ho, Wo, Cout)
-        ops.conv_igemm(x, self._pack(conv.weight, L.PACK_CONV_FWD), conv.bias.detach() if conv.bias is not None else None,
-                       y, ntaps=9, taps_mode=L.TAPS_CONV_S2)
+        ops.conv_igemm(x, self._pack(conv.weight, L.PACK_CONV_FWD), _bias_of(conv), y, ntaps=9, taps_mode=L.TAPS_CONV_S2)
         if self.record:
             def bwd():
                 g = self._total_grad(y)
@@ -785,14 +790,11 @@ class Engine:
                     gfull = self.new_act(N, H, W, Cout)        # dy between zeros: the dense stride-1 gradient routes
                     ops.resample2(g, gfull, ops.RESAMPLE_ZERO_INSERT)
                 if fast_w:
-                    dw = ops.wgrad(g, x, tuple(conv.weight.shape), ntaps=9, taps_mode=L.TAPS_CONV_S2, out=self._dst(conv.weight))
+                    self._conv_wgrad(conv, g, x, 9, tmode=L.TAPS_CONV_S2)
                 else:
-                    dw = ops.wgrad(gfull, x, tuple(conv.weight.shape), ntaps=9, out=self._dst(conv.weight))
-                self._give_grad(conv.weight, dw)
+                    self._conv_wgrad(conv, gfull, x, 9)
                 if x.needs_grad:
-                    dx = self.new_act(N, H, W, x.C)
-                    ops.conv_igemm(gfull, self._pack(conv.weight, L.PACK_CONV_DGRAD), None, dx, ntaps=9)
-                    x.add_grad(dx)
+                    x.add_grad(self._conv_dgrad(conv, gfull, 9)[0])
 
             self.tape.append(bwd)
         return y
@@ -909,7 +911,7 @@ class Engine:
                                                     taps_mode=L.TAPS_GATHER2X2, out=self._dst(m.weight)))
                 if x.needs_grad:
                     dx = self.new_act(x.N, x.H, x.W, x.C)
-                    src = getattr(x, "bn_src", None) if (sole_reader and self.fuse_bn_reduce_convt) else None
+                    src = x.bn_src if (sole_reader and self.fuse_bn_reduce_convt) else None
                     part = ops.conv_igemm(g, self._pack(m.weight, L.PACK_CONVT_DGRAD), None, dx, ntaps=4,
                                           taps_mode=L.TAPS_GATHER2X2, bnred=src)
                     if src is not None and part is not None:
@@ -939,8 +941,7 @@ class Engine:
         the two are never summed by a separate pass."""
         assert lin.in_features == x.C
         y = out if out is not None else self.new_act(x.N, x.H, x.W, lin.out_features)
-        ops.conv_igemm(x, self._pack(lin.weight, L.PACK_CONV_FWD), lin.bias.detach() if lin.bias is not None else None,
-                       y, ntaps=1, res=residual)
+        ops.conv_igemm(x, self._pack(lin.weight, L.PACK_CONV_FWD), _bias_of(lin), y, ntaps=1, res=residual)
         if self.record:
             def bwd():
                 g = self._total_grad(y)
@@ -1082,12 +1083,10 @@ class Engine:
         L.require_cuda(x)
         ps = conv.kernel_size[0]
         assert conv.kernel_size == conv.stride == (ps, ps) and x.dim() == 4 and x.shape[1] == conv.in_channels
-        K = ps * ps * conv.in_channels
-        kpad = _round_up(K, self.bk)
+        kpad = _round_up(ps * ps * conv.in_channels, self.bk)
         p = ops.patchify(x.contiguous().float(), ps, kpad, self.dtype)
         y = self.new_act(p.N, p.H, p.W, conv.out_channels)
-        ops.conv_igemm(p, self._pack(conv.weight, L.PACK_IM2COL, kpad), conv.bias.detach() if conv.bias is not None else None,
-                       y, ntaps=1)
+        ops.conv_igemm(p, self._pack(conv.weight, L.PACK_IM2COL, kpad), _bias_of(conv), y, ntaps=1)
         if self.record:
             def bwd():
                 g = self._total_grad(y)
@@ -1095,9 +1094,7 @@ class Engine:
                     return
                 if conv.bias is not None:
                     self._bias_grad(conv.bias, g)
-                dwp = ops.wgrad(g, p, (conv.out_channels, kpad), ntaps=1)
-                dw = dwp[:, :K].reshape(conv.out_channels, ps * ps, conv.in_channels).permute(0, 2, 1)
-                self._give_grad(conv.weight, dw.reshape(conv.weight.shape).contiguous())
+                self._im2col_wgrad(conv, g, p)
 
             self.tape.append(bwd)
         return y
@@ -1109,12 +1106,10 @@ class Engine:
         L.require_cuda(x)
         k, st, pd = conv.kernel_size[0], conv.stride[0], conv.padding[0]
         assert conv.kernel_size == (k, k) and conv.stride == (st, st) and conv.padding == (pd, pd) and x.shape[1] == conv.in_channels
-        K = k * k * conv.in_channels
-        kpad = _round_up(K, self.bk)
+        kpad = _round_up(k * k * conv.in_channels, self.bk)
         p = ops.im2col_nchw(x.contiguous().float(), k, st, pd, kpad, self.dtype)
         y = self.new_act(p.N, p.H, p.W, conv.out_channels)
-        ops.conv_igemm(p, self._pack(conv.weight, L.PACK_IM2COL, kpad), conv.bias.detach() if conv.bias is not None else None,
-                       y, ntaps=1)
+        ops.conv_igemm(p, self._pack(conv.weight, L.PACK_IM2COL, kpad), _bias_of(conv), y, ntaps=1)
         if self.record:
             def bwd():
                 g = self._total_grad(y)
@@ -1122,9 +1117,7 @@ class Engine:
                     return
                 if conv.bias is not None:
                     self._bias_grad(conv.bias, g)
-                dwp = ops.wgrad(g, p, (conv.out_channels, kpad), ntaps=1)
-                dw = dwp[:, :K].reshape(conv.out_channels, k * k, conv.in_channels).permute(0, 2, 1)
-                self._give_grad(conv.weight, dw.reshape(conv.weight.shape).contiguous())
+                self._im2col_wgrad(conv, g, p)
 
             self.tape.append(bwd)
         return y
@@ -1141,8 +1134,7 @@ class Engine:
         xs = self.new_act(x.N, x.H // r, x.W // r, T * x.C)
         ops.space_to_depth(x, xs, r)
         y = out if out is not None else self.new_act(xs.N, xs.H, xs.W, Cout)
-        ops.conv_igemm(xs, self._pack(conv.weight, L.PACK_CONV_FWD), conv.bias.detach() if conv.bias is not None else None,
-                       y, ntaps=1)
+        ops.conv_igemm(xs, self._pack(conv.weight, L.PACK_CONV_FWD), _bias_of(conv), y, ntaps=1)
         if self.record:
             def bwd():
                 g = self._total_grad(y)
@@ -1185,7 +1177,7 @@ class Engine:
         assert conv.groups == C == conv.in_channels == conv.out_channels and conv.kernel_size == (3, 3) and conv.padding == (1, 1)
         wt = conv.weight.detach().reshape(C, 9).t().contiguous()      # [9][C]
         y = self.new_act(x.N, x.H, x.W, C)
-        ops.dwconv3x3(x, wt, conv.bias.detach() if conv.bias is not None else None, y, skip=skip)
+        ops.dwconv3x3(x, wt, _bias_of(conv), y, skip=skip)
         if self.record:
             def bwd():
                 g = self._total_grad(y)
@@ -1982,7 +1974,7 @@ class Engine:
                     ops.sideconv_fwd(f, wp, bp, taps, lp, K * hw)
                     ops.bilinear_planes(lp, K * hw, f.H, f.W, plane, S * K * HW, H, W, N)
         wf = fuse.weight.detach().reshape(K, S * K)
-        d0 = ops.fuse1x1_fwd(dcat, wf, fuse.bias.detach() if fuse.bias is not None else None)
+        d0 = ops.fuse1x1_fwd(dcat, wf, _bias_of(fuse))
         outs = [d0] + [dcat[:, s_ * K:(s_ + 1) * K] for s_ in range(S)]
 
         if self.record:
@@ -2036,14 +2028,14 @@ class Engine:
         K = conv.out_channels
         w = conv.weight.detach().reshape(K, x.C)
         b = conv.bias.detach() if conv.bias is not None else torch.zeros(K, device=self.device)
-        xf = getattr(x, "lazy", None)      # x is the raw output of a convolution (conv_bn_relu(defer_apply=this head))
-        assert xf is None or sole_reader, "a lazy activation goes to the head it was deferred for"
+        assert x.lazy is None or sole_reader, "a lazy activation goes to the head it was deferred for"
+        xf = x.take_lazy()      # x is the raw output of a convolution (conv_bn_relu(defer_apply=this head))
         logits = ops.outconv_fwd(x, w, b, xform=xf)
         if self.record:
             def bwd(g_logits: torch.Tensor):
                 dwt = self._dst(conv.weight)
                 dbt = self._dst(conv.bias) if conv.bias is not None else None
-                src = getattr(x, "bn_src", None) if (sole_reader and (self.fuse_bn_reduce_convt or xf is not None)) else None
+                src = x.bn_src if (sole_reader and (self.fuse_bn_reduce_convt or xf is not None)) else None
                 gl = g_logits.contiguous().float()
                 # lazy head, sole reader: the rank-K gradient is not written down; the producing block's apply pass forms it
                 # from a virtual gradient (logit gradients, weights, the BatchNorm partial rows) -- where that pass takes the
@@ -2106,7 +2098,7 @@ class Engine:
             N, Ho, Wo = x.N, x.H, x.W
         gamma, beta = ln.weight.detach(), ln.bias.detach()
         w = conv.weight.detach().reshape(K, C)
-        b = conv.bias.detach() if conv.bias is not None else None
+        b = _bias_of(conv)
         logits, stats = ops.ln_head_fwd(x, gamma, beta, w, b, N, Ho, Wo, C, mode=mode, r=r, eps=ln.eps)
         if self.record:
             def bwd(g_logits: torch.Tensor):
@@ -2142,8 +2134,7 @@ class Engine:
             y = Act(torch.zeros((x.P, _round_up(Cout, 8)), dtype=self.dtype, device=self.device), 0, Cout, N, H, W)
         else:
             y = self.new_act(N, H, W, Cout)
-        stats = ops.conv5x5(x, self._pack(conv.weight, L.PACK_CONV_FWD), conv.bias.detach() if conv.bias is not None else None,
-                            y, want_stats=True)
+        stats = ops.conv5x5(x, self._pack(conv.weight, L.PACK_CONV_FWD), _bias_of(conv), y, want_stats=True)
         if self.record:
             def bwd():
                 g = self._total_grad(y)
@@ -2182,8 +2173,8 @@ class Engine:
             raise ValueError(f"Expected more than 1 value per channel when training, got input size {(N, C, H, W)}")
         if stats is None:
             stats = ops.colstats(raw)
-        mom = bn.momentum if bn.momentum is not None else 0.1
-        vec = ops.bn_finalize(stats, raw.P, bn.weight.detach(), bn.bias.detach(), bn.eps, mom, bn.running_mean, bn.running_var)
+        vec = ops.bn_finalize(stats, raw.P, bn.weight.detach(), bn.bias.detach(), bn.eps, self._momentum(bn, count=False),
+                              bn.running_mean, bn.running_var)
         if out is None:
             out = Act(torch.zeros_like(raw.buf), 0, C, N, H, W) if pad_grad else self.new_act(N, H, W, C)
         ops.bn_elu_apply(raw, vec[0], vec[1], out, act1=act1, act2=act2, res=res, out2=out2, mask2=mask2)
@@ -2204,11 +2195,7 @@ class Engine:
                 else:
                     dx = self.new_act(N, H, W, C)
                 gres = self.new_act(N, H, W, C) if (res is not None and res.needs_grad) else None
-                dgamma, dbeta = self._dst(bn.weight), self._dst(bn.bias)
-                if dgamma is None:
-                    dgamma = torch.empty(C, dtype=torch.float32, device=self.device)
-                if dbeta is None:
-                    dbeta = torch.empty(C, dtype=torch.float32, device=self.device)
+                dgamma, dbeta = self._bn_grad_dst(bn, C)
                 ops.bn_elu_bwd(raw, vec, out, gs[0], gs[1] if len(gs) > 1 else None, g2, mask2, self._bn_sums(C), dx, gres,
                                dgamma, dbeta, act1=act1, act2=act2)
                 self._give_grad(bn.weight, dgamma)

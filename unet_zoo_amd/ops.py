@@ -5,10 +5,10 @@ are never materialised).
 """
 from __future__ import annotations
 
+import ctypes
+import math
 from ctypes import byref
 from typing import List, Optional, Sequence
-
-import math
 
 import torch
 
@@ -19,10 +19,9 @@ class Act:
     """NHWC activation: element (pixel p, channel c) at ``buf[p, off + c]``; ``buf`` is (P, ld)."""
 
     __slots__ = ("buf", "off", "C", "N", "H", "W", "grads", "parts", "rparts", "needs_grad", "colsums", "bn_src",
-                 "bn_partials", "lazy")
+                 "bn_partials", "lazy", "_taken")
 
-    def __init__(self, buf: torch.Tensor, off: int, C: int, N: int, H: int, W: int,
-                 needs_grad: bool = True):
+    def __init__(self, buf: torch.Tensor, off: int, C: int, N: int, H: int, W: int, needs_grad: bool = True):
         assert buf.dim() == 2 and buf.is_contiguous() and buf.shape[0] == N * H * W
         assert 0 <= off and off + C <= buf.shape[1]
         self.buf, self.off, self.C, self.N, self.H, self.W = buf, off, C, N, H, W
@@ -30,13 +29,21 @@ class Act:
         self.parts: Optional[Sequence["Act"]] = None  # set on the full view of a concat buffer
         self.rparts: Optional[Sequence[tuple]] = None  # (part, first row): a token-concat whose producers wrote row blocks
         self.needs_grad = needs_grad
-        # optional (partials [G, 2, Ctot], channel offset): per-channel sums of this tensor that its
-        # producing kernel delivered for free (used for ConvTranspose2d bias gradients)
-        self.colsums = None
-        # (scale, shift): the buffer holds the RAW output of a convolution and stands for relu(buf * scale + shift), which
-        # nobody has written down (Engine.conv_bn_relu(defer_apply=True)); only the kernels that read through that map
-        # (conv_igemm / wgrad with xform=...) may take it
-        self.lazy = None
+        # What a producer hands to the ONE reader of its tensor: set once by the engine block named, read in the same step.
+        # colsums = (partials [G, 2, Ctot], channel offset), on a GRADIENT: its per-channel sums, left for free by the input-
+        #   gradient convolution that wrote it (conv_bn_relu's backward); the ConvTranspose2d that produced the tensor takes its
+        #   bias gradient from them (channel_sums()); window() carries them along.
+        # bn_src = (y, vec), on a conv_bn_relu OUTPUT (training, ReLU, no pool / residual): the raw convolution output and the
+        #   (scale, shift, mean, invstd) rows; read in the backward of a reader that was told sole_reader=True (conv_bn_relu,
+        #   conv_transpose2x2, out_conv), whose input-gradient kernel then runs this BatchNorm's first backward pass (bnred=).
+        # bn_partials, on a GRADIENT: the rows of that pass, set by the kernel that ran it (conv_igemm / outconv_bwd with bnred=;
+        #   HeadGrad has the same field); read by the producing conv_bn_relu's backward (bn_relu_bwd(partials=)).
+        # lazy = (scale, shift), on a conv_bn_relu(defer_apply=...) OUTPUT: the buffer holds the RAW convolution output and stands
+        #   for relu(buf * scale + shift), which nobody has written down.  Only the reader it was deferred for (conv_bn_relu /
+        #   out_conv, sole_reader=True) may have it: it takes the map ONCE (take_lazy()) and its kernels (xform=...) read the
+        #   buffer through raw_ptr(); ptr(), window(), rows() and a concat's add_grad refuse.
+        self.colsums = self.bn_src = self.bn_partials = self.lazy = None
+        self._taken = False      # take_lazy() has handed the map out
 
     @property
     def ld(self) -> int:
@@ -51,9 +58,21 @@ class Act:
         return self.buf.dtype
 
     def ptr(self) -> int:
+        assert self.lazy is None, "a lazy activation is read through its map only: by the reader it was deferred for"
+        return self.raw_ptr()
+
+    def raw_ptr(self) -> int:
+        """the address whatever the buffer holds: for the kernels that read through a lazy view's map (xform=...) and nothing else"""
         return self.buf.data_ptr() + self.off * self.buf.element_size()
 
+    def take_lazy(self) -> Optional[tuple]:
+        """the (scale, shift) map of a lazy view (None for a real tensor) for its one reader: a second take raises"""
+        assert not self._taken, "a lazy activation has ONE reader and that reader has taken it"
+        self._taken = self.lazy is not None
+        return self.lazy
+
     def window(self, off: int, C: int) -> "Act":
+        assert self.lazy is None, "a channel window of a lazy activation would drop its map"
         w = Act(self.buf, self.off + off, C, self.N, self.H, self.W, self.needs_grad)
         if self.colsums is not None:
             w.colsums = (self.colsums[0], self.colsums[1] + off)
@@ -61,6 +80,7 @@ class Act:
 
     def rows(self, r0: int, N: int, H: int, W: int) -> "Act":
         """rows [r0, r0 + N*H*W) as an (N, H, W, C) tensor of their own (token-concats along dim -2)"""
+        assert self.lazy is None, "a row block of a lazy activation would drop its map"
         return Act(self.buf[r0:r0 + N * H * W], self.off, self.C, N, H, W, self.needs_grad)
 
     def channel_sums(self, out: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
@@ -81,6 +101,7 @@ class Act:
 
     def add_grad(self, g: "Act") -> None:
         """Register a gradient contribution; a concat view forwards channel windows to its parts."""
+        assert self.lazy is None or (self.parts is None and self.rparts is None), "a concat view is never lazy"
         if self.parts is not None:
             o = 0
             for part in self.parts:
@@ -312,11 +333,29 @@ def conv_first_wgrad_bn(x: torch.Tensor, g: Act, y: Act, vec: torch.Tensor, sums
 def conv_kernel_name(d, with_workspace: bool = False) -> str:
     """uz_conv_igemm_kernel_name(): the kernel family the library's plan picks for a ConvDesc (labels of the per-kernel
     timing of bench.py; tests use it to assert which generation they exercise)"""
-    import ctypes
     buf = ctypes.create_string_buffer(96)
     L.check_count(L.load().uz_conv_igemm_kernel_name(byref(d), 1 if with_workspace else 0, buf, 96),
                   "uz_conv_igemm_kernel_name")
     return buf.value.decode()
+
+
+def _conv_desc(x: Act, nout: int, ldy: int, ntaps: int, taps_mode: int, dil: int = 1, store_mode: int = L.STORE_PLAIN,
+               co: int = 0, Hd: int = 0, Wd: int = 0):
+    """the ConvDesc of a convolution of x to nout channels; the output grid follows from taps_mode"""
+    if taps_mode == L.TAPS_CONV:
+        H, W = x.H, x.W
+    elif taps_mode == L.TAPS_CONV_UP2:       # x is the half-resolution tensor
+        H, W = 2 * x.H, 2 * x.W
+    elif taps_mode == L.TAPS_CONV_S2:        # Conv2d(k3, stride 2, padding 1): ceil(H / 2)
+        H, W = (x.H + 1) // 2, (x.W + 1) // 2
+    else:
+        H, W = x.H // 2, x.W // 2
+    return L.ConvDesc(L.dtype_code(x.dtype), x.N, H, W, x.H, x.W, x.C, x.ld, nout, ldy, ntaps, taps_mode, dil, store_mode, co,
+                      Hd, Wd)
+
+
+def _wgrad_desc(Lt: Act, Rt: Act, ntaps: int, taps_mode: int = L.TAPS_CONV, dil: int = 1):
+    return L.WgradDesc(L.dtype_code(Lt.dtype), Lt.N, Lt.H, Lt.W, Rt.H, Rt.W, Lt.C, Lt.ld, Rt.C, Rt.ld, ntaps, taps_mode, dil)
 
 
 def conv_igemm(x: Act, w_packed: torch.Tensor, bias: Optional[torch.Tensor], y: Act, *,
@@ -334,17 +373,8 @@ def conv_igemm(x: Act, w_packed: torch.Tensor, bias: Optional[torch.Tensor], y: 
     conv_xform_supported() first."""
     L.require_cuda(x.buf, w_packed, y.buf)
     lib = L.load()
-    if taps_mode == L.TAPS_CONV:
-        N, H, W = x.N, x.H, x.W
-    elif taps_mode == L.TAPS_CONV_UP2:       # x is the half-resolution tensor
-        N, H, W = x.N, 2 * x.H, 2 * x.W
-    elif taps_mode == L.TAPS_CONV_S2:        # Conv2d(k3, stride 2, padding 1): ceil(H / 2)
-        N, H, W = x.N, (x.H + 1) // 2, (x.W + 1) // 2
-    else:
-        N, H, W = x.N, x.H // 2, x.W // 2
     shuffle = store_mode == L.STORE_SHUFFLE2X2   # destination grid may be one row / column larger (zero pad)
-    d = L.ConvDesc(L.dtype_code(x.dtype), N, H, W, x.H, x.W, x.C, x.ld,
-                   nout if nout is not None else y.C, y.ld, ntaps, taps_mode, dil, store_mode, co,
+    d = _conv_desc(x, nout if nout is not None else y.C, y.ld, ntaps, taps_mode, dil, store_mode, co,
                    y.H if shuffle else 0, y.W if shuffle else 0)
     assert w_packed.dtype == x.dtype and y.dtype == x.dtype
     assert w_packed.shape == (d.Nout, ntaps * x.C), (tuple(w_packed.shape), d.Nout, ntaps, x.C)
@@ -354,12 +384,12 @@ def conv_igemm(x: Act, w_packed: torch.Tensor, bias: Optional[torch.Tensor], y: 
         stats = torch.empty((gm, 2, d.Nout), dtype=torch.float32, device=x.buf.device)
     wsb = L.check_count(lib.uz_conv_igemm_workspace_bytes(byref(d)), "uz_conv_igemm_workspace_bytes")
     ws = torch.empty(wsb // 4, dtype=torch.float32, device=x.buf.device) if wsb > 0 else None
-    M, K, es = N * H * W, ntaps * x.C, x.buf.element_size()
+    M, K, es = d.N * d.H * d.W, ntaps * x.C, x.buf.element_size()
     kname = conv_kernel_name(d, ws is not None)   # the family the library's own plan launches for this descriptor
     if xform is not None:
         assert bnred is None and res is None
         with _Timed(kname + "_xf", 2.0 * M * d.Nout * K, es * (x.P * x.C + M * d.Nout + d.Nout * K)):
-            L.check(lib.uz_conv_igemm_xf(byref(d), x.ptr(), xform[0].data_ptr(), xform[1].data_ptr(), w_packed.data_ptr(),
+            L.check(lib.uz_conv_igemm_xf(byref(d), x.raw_ptr(), xform[0].data_ptr(), xform[1].data_ptr(), w_packed.data_ptr(),
                                          _p(bias), y.ptr(), _p(stats), L.stream_ptr()), "uz_conv_igemm_xf")
         return stats
     if bnred is not None:
@@ -392,17 +422,11 @@ def conv_igemm(x: Act, w_packed: torch.Tensor, bias: Optional[torch.Tensor], y: 
     return stats
 
 
-def _bnact_desc(x: Act, nout: int, ldy: int, ntaps: int, dil: int, taps_mode: int):
-    H, W = (2 * x.H, 2 * x.W) if taps_mode == L.TAPS_CONV_UP2 else (x.H, x.W)
-    return L.ConvDesc(L.dtype_code(x.dtype), x.N, H, W, x.H, x.W, x.C, x.ld, nout, ldy, ntaps, taps_mode, dil,
-                      L.STORE_PLAIN, 0, 0, 0)
-
-
 def conv_bnact_supported(x: Act, nout: int, ldy: int, *, ntaps: int, dil: int = 1, taps_mode: int = L.TAPS_CONV) -> bool:
     """whether uz_conv_igemm_bnact takes the convolution of x to nout channels (eval-mode BatchNorm [+ ReLU] in the epilogue)"""
     if taps_mode not in (L.TAPS_CONV, L.TAPS_CONV_UP2):
         return False
-    d = _bnact_desc(x, nout, ldy, ntaps, dil, taps_mode)
+    d = _conv_desc(x, nout, ldy, ntaps, taps_mode, dil)
     return bool(L.load().uz_conv_igemm_bnact_supported(byref(d)))
 
 
@@ -411,7 +435,7 @@ def conv_igemm_bnact(x: Act, w_packed: torch.Tensor, bias: Optional[torch.Tensor
     """y = relu?(fma(conv(x, w) + bias, scale, shift)) in one launch, rounded once (uz_conv_igemm_bnact): the convolution with
     the eval-mode BatchNorm [+ ReLU] behind it; the caller has asked conv_bnact_supported() first.  No fallback."""
     L.require_cuda(x.buf, w_packed, y.buf, scale, shift)
-    d = _bnact_desc(x, y.C, y.ld, ntaps, dil, taps_mode)
+    d = _conv_desc(x, y.C, y.ld, ntaps, taps_mode, dil)
     assert w_packed.dtype == x.dtype and y.dtype == x.dtype and (y.N, y.H, y.W) == (d.N, d.H, d.W)
     assert w_packed.shape == (d.Nout, ntaps * x.C), (tuple(w_packed.shape), d.Nout, ntaps, x.C)
     assert scale.dtype == shift.dtype == torch.float32 and scale.numel() == shift.numel() == d.Nout
@@ -440,16 +464,13 @@ def conv_first_fwd_bnact(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.
 
 def conv_xform_supported(x: Act, nout: int, ldy: int, *, upsample: bool = False) -> bool:
     """whether uz_conv_igemm_xf takes the 3x3 convolution of x (channels, pixel grid, run dtype) to nout channels"""
-    H, W = (2 * x.H, 2 * x.W) if upsample else (x.H, x.W)
-    d = L.ConvDesc(L.dtype_code(x.dtype), x.N, H, W, x.H, x.W, x.C, x.ld, nout, ldy, 9,
-                   L.TAPS_CONV_UP2 if upsample else L.TAPS_CONV, 1, L.STORE_PLAIN, 0, 0, 0)
+    d = _conv_desc(x, nout, ldy, 9, L.TAPS_CONV_UP2 if upsample else L.TAPS_CONV)
     return bool(L.load().uz_conv_igemm_xf_supported(byref(d)))
 
 
 def wgrad_kernel_name(d) -> str:
     """uz_wgrad_kernel_name(): the kernel family the library's plan picks for a WgradDesc (labels of bench.py's per-kernel
     timing; tests use it to assert which kernel they exercise)"""
-    import ctypes
     buf = ctypes.create_string_buffer(96)
     L.check_count(L.load().uz_wgrad_kernel_name(byref(d), buf, 96), "uz_wgrad_kernel_name")
     return buf.value.decode()
@@ -457,14 +478,14 @@ def wgrad_kernel_name(d) -> str:
 
 def wgrad_xform_supported(Lt: Act, Rt: Act, ntaps: int, *, taps_mode: int = L.TAPS_CONV, dil: int = 1) -> bool:
     """whether uz_wgrad_xf takes this weight-gradient problem (R read through a BatchNorm + ReLU)"""
-    d = L.WgradDesc(L.dtype_code(Lt.dtype), Lt.N, Lt.H, Lt.W, Rt.H, Rt.W, Lt.C, Lt.ld, Rt.C, Rt.ld, ntaps, taps_mode, dil)
-    return bool(L.load().uz_wgrad_xf_supported(byref(d)))
+    return bool(L.load().uz_wgrad_xf_supported(byref(_wgrad_desc(Lt, Rt, ntaps, taps_mode, dil))))
 
 
 def wgrad_xform_shapes_supported(N: int, H: int, W: int, Ci: int, ldl: int, Cj: int, ldr: int, dtype: torch.dtype) -> bool:
     """the same question before the output gradient exists: a (N, H, W, Ci) gradient against a (N, H, W, Cj) raw input"""
-    d = L.WgradDesc(L.dtype_code(dtype), N, H, W, H, W, Ci, ldl, Cj, ldr, 9, L.TAPS_CONV, 1)
-    return bool(L.load().uz_wgrad_xf_supported(byref(d)))
+    def shape(C, ld):      # an Act without storage
+        return Act(torch.empty((N * H * W, ld), dtype=dtype, device="meta"), 0, C, N, H, W)
+    return wgrad_xform_supported(shape(Ci, ldl), shape(Cj, ldr), 9)
 
 
 def wgrad(Lt: Act, Rt: Act, out_shape, *, ntaps: int, dil: int = 1,
@@ -474,39 +495,32 @@ def wgrad(Lt: Act, Rt: Act, out_shape, *, ntaps: int, dil: int = 1,
     layer's BatchNorm + ReLU (uz_wgrad_xf; ask wgrad_xform_supported first)."""
     L.require_cuda(Lt.buf, Rt.buf)
     lib = L.load()
-    d = L.WgradDesc(L.dtype_code(Lt.dtype), Lt.N, Lt.H, Lt.W, Rt.H, Rt.W, Lt.C, Lt.ld, Rt.C, Rt.ld,
-                    ntaps, taps_mode, dil)
+    d = _wgrad_desc(Lt, Rt, ntaps, taps_mode, dil)
     ws_bytes = L.check_count(lib.uz_wgrad_workspace_bytes(byref(d)), "uz_wgrad_workspace_bytes")
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=Lt.buf.device)
     if out is None:
         out = torch.empty(out_shape, dtype=torch.float32, device=Lt.buf.device)
     assert out.numel() == Lt.C * Rt.C * ntaps and out.is_contiguous() and out.dtype == torch.float32
-    if xform is not None:
-        def run(phase):
-            L.check(lib.uz_wgrad_xf(byref(d), Lt.ptr(), Rt.ptr(), xform[0].data_ptr(), xform[1].data_ptr(), out.data_ptr(),
+    def run(phase):     # 0: the whole product; 1, 2: the main kernel and the slab reduction on their own
+        if xform is not None:
+            L.check(lib.uz_wgrad_xf(byref(d), Lt.ptr(), Rt.raw_ptr(), xform[0].data_ptr(), xform[1].data_ptr(), out.data_ptr(),
                                     ws.data_ptr(), L.stream_ptr(), phase), "uz_wgrad_xf")
-        if not _prof_on:
-            run(0)
-            return out
-        with _Timed(wgrad_kernel_name(d) + "_xf", 2.0 * Lt.P * Lt.C * Rt.C * ntaps,
-                    Lt.buf.element_size() * (Lt.P * Lt.C + Rt.P * Rt.C) + 4.0 * out.numel()):
-            run(1)
-        with _Timed("wgrad_reduce", 0.0, float(ws_bytes) + 4.0 * out.numel()):
-            run(2)
-        return out
+        elif phase == 0:
+            L.check(lib.uz_wgrad(byref(d), Lt.ptr(), Rt.ptr(), out.data_ptr(), ws.data_ptr(), L.stream_ptr()), "uz_wgrad")
+        else:
+            L.check(lib.uz_wgrad_phase(byref(d), Lt.ptr(), Rt.ptr(), out.data_ptr(), ws.data_ptr(), L.stream_ptr(), phase),
+                    "uz_wgrad_phase")
     if not _prof_on:
-        L.check(lib.uz_wgrad(byref(d), Lt.ptr(), Rt.ptr(), out.data_ptr(), ws.data_ptr(), L.stream_ptr()), "uz_wgrad")
+        run(0)
         return out
     # measured (bench.py's eager profile steps): the main kernel and the slab reduction in brackets of their own, so that
     # a family's average launch time is ONE kernel's, as a kernel trace reports it
-    kname = wgrad_kernel_name(d)   # the family the library's own plan launches for this descriptor
+    kname = wgrad_kernel_name(d) + ("_xf" if xform is not None else "")   # the family the library's own plan launches
     with _Timed(kname, 2.0 * Lt.P * Lt.C * Rt.C * ntaps,
                 Lt.buf.element_size() * (Lt.P * Lt.C + Rt.P * Rt.C) + 4.0 * out.numel()):
-        L.check(lib.uz_wgrad_phase(byref(d), Lt.ptr(), Rt.ptr(), out.data_ptr(), ws.data_ptr(), L.stream_ptr(), 1),
-                "uz_wgrad_phase")
+        run(1)
     with _Timed("wgrad_reduce", 0.0, float(ws_bytes) + 4.0 * out.numel()):
-        L.check(lib.uz_wgrad_phase(byref(d), Lt.ptr(), Rt.ptr(), out.data_ptr(), ws.data_ptr(), L.stream_ptr(), 2),
-                "uz_wgrad_phase")
+        run(2)
     return out
 
 
@@ -521,8 +535,7 @@ def wgrad_multi(entries: Sequence) -> None:
     for i, (Lt, Rt, out, ntaps, taps_mode, dil) in enumerate(entries):
         L.require_cuda(Lt.buf, Rt.buf, out)
         assert out.numel() == Lt.C * Rt.C * ntaps and out.is_contiguous() and out.dtype == torch.float32
-        d = L.WgradDesc(L.dtype_code(Lt.dtype), Lt.N, Lt.H, Lt.W, Rt.H, Rt.W, Lt.C, Lt.ld, Rt.C, Rt.ld, ntaps, taps_mode, dil)
-        arr[i] = L.WgradItem(d, Lt.ptr(), Rt.ptr(), out.data_ptr())
+        arr[i] = L.WgradItem(_wgrad_desc(Lt, Rt, ntaps, taps_mode, dil), Lt.ptr(), Rt.ptr(), out.data_ptr())
         flops += 2.0 * Lt.P * Lt.C * Rt.C * ntaps
         nbytes += Lt.buf.element_size() * (Lt.P * Lt.C + Rt.P * Rt.C) + 4.0 * out.numel()
     ws_bytes = L.check_count(lib.uz_wgrad_multi_workspace_bytes(arr, len(entries)), "uz_wgrad_multi_workspace_bytes")
@@ -752,7 +765,7 @@ def outconv_fwd(x: Act, w: torch.Tensor, b: torch.Tensor, xform: Optional[tuple]
     out = torch.empty((x.N, K, x.H, x.W), dtype=torch.float32, device=x.buf.device)
     if xform is not None:
         assert outconv_xform_supported(x, K)
-        L.check(lib.uz_outconv_fwd_xf(L.dtype_code(x.dtype), x.ptr(), x.ld, x.N, x.H * x.W, x.C, xform[0].data_ptr(),
+        L.check(lib.uz_outconv_fwd_xf(L.dtype_code(x.dtype), x.raw_ptr(), x.ld, x.N, x.H * x.W, x.C, xform[0].data_ptr(),
                                       xform[1].data_ptr(), w.data_ptr(), b.data_ptr(), K, out.data_ptr(), L.stream_ptr()),
                 "uz_outconv_fwd_xf")
         return out
@@ -1058,7 +1071,6 @@ def fuse1x1_fwd(d: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]) -> 
 
 def fuse1x1_bwd(d: torch.Tensor, w: torch.Tensor, g: Optional[torch.Tensor], extras: Sequence[Optional[torch.Tensor]],
                 dw: torch.Tensor, db: Optional[torch.Tensor]) -> torch.Tensor:
-    import ctypes
     lib = L.load()
     N, Cc, H, W = d.shape
     K = w.shape[0]
