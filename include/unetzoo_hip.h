@@ -776,6 +776,64 @@ int uz_region_loss(const uz_region_desc* d, const uz_region_item* items, float* 
                    void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Softmax cross-entropy + soft Dice over several output maps at once: the multi-class counterpart of
+ * uz_region_loss.  uz_class_loss.hip
+ * Per map: logits x (N, K, HW) fp32, contiguous; the labels y (N, HW) int32 are shared by all maps.  A pixel is VALID
+ * when y != ignore_index and 0 <= y < K; a label outside [0, K) that is not ignore_index is treated as ignored and
+ * counted (counts, below).  p = softmax_K(x), w = class_weight (NULL: ones), e = label_smoothing:
+ *   a_c(i) = (1 - e) w_c [c == y_i] + (e / K) w_c
+ *   CE     = sum_valid sum_c a_c(i) (-log p_c(i)) / sum_valid w_{y_i}          (F.cross_entropy with mean reduction;
+ *                                                                               0 with zero gradient when no pixel is valid)
+ *   I, S, T = sum p_c [y == c], sum p_c (square: sum p_c^2), sum [y == c]       over the valid pixels of group g
+ *   dice   = mean_{g, c in C} (1 - (2 I + smooth) / (S + T + smooth))          formed as (S + T - 2 I) / denominator
+ *            g: the batch (reduce = UZ_CLASS_REDUCE_BATCH) or each image (UZ_CLASS_REDUCE_IMAGE);
+ *            C: all classes, or 1 .. K-1 when include_background == 0
+ *   out2[0] = sum_m items[m].weight * (w_ce * CE_m + w_dice * dice_m)
+ *   out2[1] = of map `metric_item`, prediction argmax_K x (ties: the lowest index), over the valid pixels of the batch:
+ *             mean over the classes of C with P_c + T_c > 0 of 2 TP_c / (P_c + T_c); 1 when no class remains
+ *   counts (nullable): K + 1 rows of 3 -- TP_c, P_c, T_c per class of that map, then (valid, ignored, out of range)
+ *   items[m].dlogits (nullable) = d(out2[0]) / d(items[m].logits); exactly 0 at pixels that are not valid
+ * Launches, whatever n_items is: (1) one row of 4 + 5 K doubles per workgroup (sum CE terms, sum w_y, valid, out of
+ * range; per class I, S, T, TP, P), every workgroup inside one image of one map, one lane per run of four pixels
+ * walking the K planes; (2) one workgroup totals the rows in a fixed order and writes out2, counts and per (map, image)
+ * the factor weight w_ce / W and per class the coefficients (u, v) of d(loss)/d(p_c) = u [y == c] + v (square: 2 p_c v);
+ * (3) the gradient dlogits_k = p_k (g_k - sum_c p_c g_c) + weight w_ce (p_k sum_c a_c - a_k) / W, the softmax
+ * recomputed -- not launched when every dlogits is NULL.  No atomics, no memset, no host read; the workspace is written
+ * before it is read in every call; two calls on the same inputs give the same bits.  16-byte loads when HW is a
+ * multiple of 4 and every pointer is 16-byte aligned, scalar loads of the same runs otherwise: the same numbers.  Above
+ * 16 classes a lane takes one pixel at a time (4-byte loads on both paths): four pixels of 32 classes do not fit the
+ * registers.
+ * `items` is a HOST array copied into the kernel arguments (as uz_region_loss's).
+ * UZ_EINVAL before any launch: null descriptor / items / labels / out2 / workspace / logits, K outside
+ * [2, UZ_CLASS_MAX_K], n_items outside [1, UZ_CLASS_MAX_ITEMS], N or HW <= 0, smooth <= 0, label_smoothing outside
+ * [0, 1), w_ce / w_dice / an item's weight negative, w_ce = w_dice = 0, reduce not one of the two, metric_item outside
+ * [0, n_items), a workspace that is not 16-byte aligned. */
+#define UZ_CLASS_MAX_ITEMS 16
+#define UZ_CLASS_MAX_K 32
+#define UZ_CLASS_REDUCE_BATCH 0
+#define UZ_CLASS_REDUCE_IMAGE 1
+typedef struct uz_class_item {
+  const float* logits;
+  float* dlogits; /* nullable */
+  float weight;
+} uz_class_item;
+typedef struct uz_class_desc {
+  int n_items;
+  int N, K;
+  long long HW;
+  float w_ce, w_dice, smooth, label_smoothing;
+  int ignore_index;
+  int reduce;             /* UZ_CLASS_REDUCE_* */
+  int include_background; /* 0: the Dice term and the metric leave class 0 out */
+  int square;             /* S = sum p^2 */
+  int metric_item;
+} uz_class_desc;
+long long uz_class_loss_workspace_bytes(const uz_class_desc* d); /* < 0: refused */
+int uz_class_loss(const uz_class_desc* d, const uz_class_item* items, const int* labels,
+                  const float* class_weight /* K floats on the device, nullable */, float* out2 /* loss, dice */,
+                  long long* counts /* (K + 1) x 3, nullable */, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Bias gradients of a whole backward pass (or phase) in two launches.  uz_colsum.hip
  * out_i[c] = sum_p x_i[p*ld + c] (fp32) for n tensors of the run dtype: what `uz_colsum_ws` computes for one
  * nn.Linear / Conv2d bias (db = sum over tokens of the output gradient), for all of them at once; `items` is a

@@ -55,6 +55,7 @@ EXPORTS = (
     "uz_bn_elu_apply", "uz_bn_elu_bwd_rows", "uz_bn_elu_bwd_reduce", "uz_bn_elu_bwd_apply",
     "uz_conv_igemm_bnact_supported", "uz_conv_igemm_bnact", "uz_conv3x3_first_fwd_bnact",
     "uz_region_loss_workspace_bytes", "uz_region_loss",
+    "uz_class_loss_workspace_bytes", "uz_class_loss",
 )
 
 
@@ -156,6 +157,23 @@ class RegionDesc(Structure):
     _fields_ = [("n_items", c_int), ("n", ctypes.c_longlong), ("groups", c_int)] \
         + [(n, c_float) for n in ("w_bce", "w_region", "alpha", "beta", "smooth", "gamma", "pos_weight")] \
         + [("metric_item", c_int)]
+
+
+CLASS_MAX_ITEMS = 16
+CLASS_MAX_K = 32
+CLASS_REDUCE_BATCH, CLASS_REDUCE_IMAGE = 0, 1
+
+
+class ClassItem(Structure):
+    """uz_class_item: one output map of a uz_class_loss call"""
+    _fields_ = [("logits", c_void_p), ("dlogits", c_void_p), ("weight", c_float)]
+
+
+class ClassDesc(Structure):
+    """uz_class_desc"""
+    _fields_ = [("n_items", c_int), ("N", c_int), ("K", c_int), ("HW", ctypes.c_longlong)] \
+        + [(n, c_float) for n in ("w_ce", "w_dice", "smooth", "label_smoothing")] \
+        + [(n, c_int) for n in ("ignore_index", "reduce", "include_background", "square", "metric_item")]
 
 
 class HipLibraryError(RuntimeError):
@@ -338,6 +356,8 @@ def load():
     lib.uz_bn_elu_bwd_apply.argtypes = [POINTER(BnEluBwdDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.uz_region_loss_workspace_bytes.argtypes = [POINTER(RegionDesc)]
     lib.uz_region_loss.argtypes = [POINTER(RegionDesc), POINTER(RegionItem), vp, vp, vp]
+    lib.uz_class_loss_workspace_bytes.argtypes = [POINTER(ClassDesc)]
+    lib.uz_class_loss.argtypes = [POINTER(ClassDesc), POINTER(ClassItem), vp, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("uz_last_error_string", "uz_source_hash"):
@@ -376,6 +396,22 @@ def region_loss(desc: "RegionDesc", items, out2: torch.Tensor, workspace: torch.
     kernel arguments), out2 a 2-element fp32 device tensor (loss, dice).  Every call of the loss goes through here."""
     check(load().uz_region_loss(ctypes.byref(desc), items, out2.data_ptr(), workspace.data_ptr(), stream_ptr()),
           "uz_region_loss")
+
+
+def class_loss_workspace_bytes(desc: "ClassDesc") -> int:
+    """uz_class_loss_workspace_bytes(): bytes of workspace a uz_class_loss call with this descriptor needs"""
+    return check_count(load().uz_class_loss_workspace_bytes(ctypes.byref(desc)), "uz_class_loss_workspace_bytes")
+
+
+def class_loss(desc: "ClassDesc", items, labels: torch.Tensor, class_weight, out2: torch.Tensor, counts: torch.Tensor,
+               workspace: torch.Tensor) -> None:
+    """uz_class_loss() on the current stream: `items` is a ctypes array of ClassItem (a HOST table, copied into the kernel
+    arguments), labels an int32 (N, HW) device tensor, class_weight K fp32 on the device or None, out2 a 2-element fp32
+    device tensor (loss, dice), counts a (K + 1, 3) int64 device tensor.  Every call of the loss goes through here."""
+    check(load().uz_class_loss(ctypes.byref(desc), items, labels.data_ptr(),
+                               class_weight.data_ptr() if class_weight is not None else None, out2.data_ptr(),
+                               counts.data_ptr() if counts is not None else None, workspace.data_ptr(), stream_ptr()),
+          "uz_class_loss")
 
 
 def set_cu_reserve(n: int) -> None:

@@ -40,7 +40,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from .engine import Engine
-from .loss import RegionLoss, loss_and_dice
+from .loss import MulticlassLoss, RegionLoss, loss_and_dice
 from .step import CAPTURE_MODE, _check_capture, _new_graph, _unwrap
 
 
@@ -50,7 +50,7 @@ class _EvalGraph:
 
 
 class GraphedEval:
-    def __init__(self, model: nn.Module, criterion: Union[str, RegionLoss, Callable] = "bce_dice", *, fold_bn: bool = False):
+    def __init__(self, model: nn.Module, criterion: Union[str, RegionLoss, MulticlassLoss, Callable] = "bce_dice", *, fold_bn: bool = False):
         self.model = _unwrap(model)
         if isinstance(criterion, str):
             if criterion != "bce_dice":
@@ -58,9 +58,10 @@ class GraphedEval:
             self._fused_loss = True
             self._loss_fn = None
             self._fused = loss_and_dice
-        elif isinstance(criterion, RegionLoss):
-            # uz_region_loss: deterministic, no library reduction -- inside the graph, where "bce_dice" sits (two launches: no
-            # gradient is asked for); with several ranks each evaluates its own shard, so reduce="batch" is per shard
+        elif isinstance(criterion, (RegionLoss, MulticlassLoss)):
+            # uz_region_loss / uz_class_loss: deterministic, no library reduction -- inside the graph, where "bce_dice" sits
+            # (two launches: no gradient is asked for); with several ranks each evaluates its own shard, so reduce="batch" is
+            # per shard
             self._fused_loss = True
             self._loss_fn = None
             self._fused = criterion.loss_and_dice
@@ -69,6 +70,8 @@ class GraphedEval:
             # stack, exactly as in GraphedStep
             self._fused_loss = False
             self._loss_fn = criterion
+        # the static target buffer: float32 masks, or what the criterion asks for (MulticlassLoss: int32 class indices)
+        self._target_dtype = getattr(criterion, "target_dtype", torch.float32)
         self.fold_bn = bool(fold_bn)
         self._graphs: Dict[tuple, _EvalGraph] = {}
         self._sig: Optional[tuple] = None
@@ -119,7 +122,8 @@ class GraphedEval:
         with torch.cuda.stream(side):
             warm = self._forward(x)
             if self._fused_loss and self._fused is not loss_and_dice:
-                with torch.no_grad():      # a RegionLoss keeps its workspace per shape: allocated here, outside the capture
+                with torch.no_grad():      # a RegionLoss / MulticlassLoss keeps its workspace (counts, class weights) per shape:
+                    # allocated here, outside the capture
                     self._fused(warm, t)
             del warm
             # weight copies registered by that forward leave the pack cache without its pointer tables: build them now
@@ -136,7 +140,7 @@ class GraphedEval:
         with torch.cuda.graph(g.graph, capture_error_mode=CAPTURE_MODE):
             g.outputs = self._forward(g.x)
             if self._fused_loss:
-                with torch.no_grad():      # no gradient: uz_bce_dice / uz_region_loss run with dlogits = NULL
+                with torch.no_grad():      # no gradient: uz_bce_dice / uz_region_loss / uz_class_loss run with dlogits = NULL
                     g.loss, g.dice = self._fused(g.outputs, g.t)
         _check_capture(g.graph, "evaluation graph")
         g.folded, g.unfolded = self._last_counts
@@ -154,9 +158,10 @@ class GraphedEval:
         g = self._graphs.get(key)
         if g is None:
             # static input buffers of this shape (fp32 on the model's device, what `.float().to(device)` of
-            # training_loop.py:166-167 produces); later calls copy into them -- host tensors included
+            # training_loop.py:166-167 produces; the target in the criterion's target_dtype where it names one); later calls
+            # copy into them -- host tensors included
             sx = x.detach().to(device=dev, dtype=torch.float32, copy=True)
-            st = target.detach().to(device=dev, dtype=torch.float32, copy=True)
+            st = target.detach().to(device=dev, dtype=self._target_dtype, copy=True)
             g = self._graphs[key] = self._capture(sx, st)
             self._sig = self._signature()      # (the warm-up forward may have built the pack cache's tables)
         else:                                  # (a fresh capture's static buffers were created from this very batch)

@@ -7,7 +7,7 @@ scalars; nothing synchronises with the host until the caller asks for the number
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 
@@ -290,4 +290,243 @@ class RegionLoss:
     def __repr__(self) -> str:
         return (f"RegionLoss(w_bce={self.w_bce}, w_region={self.w_region}, alpha={self.alpha}, beta={self.beta}, "
                 f"smooth={self.smooth}, gamma={self.gamma}, reduce={self.reduce!r}, pos_weight={self.pos_weight}, "
+                f"output_weights={self.output_weights})")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Softmax cross-entropy + soft Dice over class-index labels: uz_class_loss, three launches for any number of output maps
+# ---------------------------------------------------------------------------------------------------------------------
+_CLASS_REDUCES = {"batch": L.CLASS_REDUCE_BATCH, "image": L.CLASS_REDUCE_IMAGE}
+_INT_DTYPES = (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64)
+
+
+class _MulticlassFn(torch.autograd.Function):
+    """ONE node for all output maps: forward is one uz_class_loss call that also writes every map's gradient"""
+
+    @staticmethod
+    def forward(ctx, crit: "MulticlassLoss", target: torch.Tensor, weights: tuple, main: int, *logits: torch.Tensor):
+        loss, dice, dl = crit._launch(logits, target, weights, main, ctx.needs_input_grad[4:])
+        ctx.dl = dl
+        ctx.in_dtypes = tuple(v.dtype for v in logits)
+        ctx.mark_non_differentiable(dice)
+        return loss, dice
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_dice):
+        return (None, None, None, None) + tuple(None if d is None else (d * g_loss).to(dt)
+                                                for d, dt in zip(ctx.dl, ctx.in_dtypes))
+
+
+class MulticlassLoss:
+    """``w_ce * CrossEntropy + w_dice * Dice`` over softmax probabilities on the device, for every output container of the zoo.
+
+    Per output map (logits ``x`` of shape ``(N, K, H, W)``, labels ``y`` of shape ``(N, H, W)`` or ``(N, 1, H, W)`` holding
+    class indices of any integer dtype; ``p = softmax_K(x)``, ``w = class_weight`` or ones, ``e = label_smoothing``).  A pixel
+    is VALID when ``y != ignore_index`` and ``0 <= y < K``; a label outside ``[0, K)`` that is not ``ignore_index`` is treated
+    as ignored and counted in ``.counts`` (no device assert)::
+
+        a_c(i)  = (1 - e) w_c [c == y_i] + (e / K) w_c
+        CE      = sum_valid sum_c a_c(i) (-log p_c(i)) / sum_valid w_{y_i}
+                  -- F.cross_entropy(x, y, weight=w, ignore_index=..., label_smoothing=e); but 0 with zero gradient, not NaN,
+                  when no pixel is valid
+        I, S, T = sum p_c [y == c], sum p_c (square=True: sum p_c^2), sum [y == c]     over the valid pixels of group g
+                  reduce="batch": one group; "image": one per image
+        dice    = mean over g and c in C of (1 - (2 I + smooth) / (S + T + smooth))
+                  C: all classes, or 1 .. K-1 with include_background=False
+        loss    = w_ce * CE + w_dice * dice
+
+    ``MulticlassLoss.ce_dice()`` is the published Swin-UNet / TransUNet recipe ``0.4 CE + 0.6 Dice`` with ``square=True``,
+    ``smooth=1e-5``, ``reduce="batch"``.
+
+    For a dict (u2net) or a list (nested_unet with deep supervision) the loss is ``sum_m output_weights[m] * loss(map_m)``, as
+    in ``RegionLoss``.  The Dice METRIC returned beside the loss is computed from the MAIN map (first value of a dict, last
+    element of a list): prediction ``argmax_K x`` (ties: the lowest index), per class over the valid pixels of the batch
+    ``2 TP_c / (P_c + T_c)``, averaged over the classes of C that occur in prediction or labels; 1 when none does.
+    ``.counts`` is the last call's ``(K + 1, 3)`` int64 device tensor of that map: rows ``TP_c, P_c, T_c``, then
+    ``(valid, ignored, out of range)`` -- sum it over an epoch for dataset-level Dice / IoU.
+
+    One call is one ``uz_class_loss``: three launches whatever the number of maps (two without gradients), fixed summation
+    order, no library reduction -- ``GraphedStep(model, MulticlassLoss(...))`` and ``GraphedEval`` keep it INSIDE their graphs
+    and hold the labels in an int32 static buffer (``target_dtype``).  In a data-parallel step every rank evaluates the loss on
+    its own shard: ``reduce="batch"`` is per shard.
+
+    Workspace, counts and the class-weight copy of a (number of maps, shape, device) are kept: calls of one object must
+    follow each other on one stream or be ordered by the caller, and ``.counts`` is overwritten by the next call.
+    The descriptor of such a plan is built at the first call with that (number of maps, shape, device): the settings are the
+    constructor's, and changing an attribute of the object afterwards has no effect on shapes already seen -- build a new
+    object instead.  ``GraphedStep`` / ``GraphedEval`` warm the criterion up outside the capture for the first shape; a
+    further input shape allocates its workspace and counts during its own capture (from the graph's pool), as
+    ``RegionLoss`` does.
+    """
+
+    target_dtype = torch.int32
+
+    def __init__(self, w_ce: float = 1.0, w_dice: float = 1.0, smooth: float = 1.0, label_smoothing: float = 0.0,
+                 class_weight=None, ignore_index: int = -100, include_background: bool = True, reduce: str = "image",
+                 square: bool = False, output_weights=None):
+        def num(name, v):
+            try:
+                f = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"MulticlassLoss: {name} must be a number, got {v!r}") from None
+            if f != f or f in (float("inf"), float("-inf")):
+                raise ValueError(f"MulticlassLoss: {name} must be finite, got {v!r}")
+            return f
+        self.w_ce, self.w_dice = num("w_ce", w_ce), num("w_dice", w_dice)
+        self.smooth, self.label_smoothing = num("smooth", smooth), num("label_smoothing", label_smoothing)
+        if self.w_ce < 0 or self.w_dice < 0:
+            raise ValueError(f"MulticlassLoss: w_ce and w_dice must be >= 0, got {w_ce!r}, {w_dice!r}")
+        if self.w_ce == 0 and self.w_dice == 0:
+            raise ValueError("MulticlassLoss: w_ce and w_dice are both zero")
+        if self.smooth <= 0:
+            raise ValueError(f"MulticlassLoss: smooth must be > 0, got {smooth!r}")
+        if not 0 <= self.label_smoothing < 1:
+            raise ValueError(f"MulticlassLoss: label_smoothing must be in [0, 1), got {label_smoothing!r}")
+        if isinstance(ignore_index, bool) or not isinstance(ignore_index, int) or not -2 ** 31 <= ignore_index < 2 ** 31:
+            raise ValueError(f"MulticlassLoss: ignore_index must be an int32 value, got {ignore_index!r}")
+        self.ignore_index = ignore_index
+        if reduce not in _CLASS_REDUCES:
+            raise ValueError(f"MulticlassLoss: reduce must be one of {tuple(_CLASS_REDUCES)}, got {reduce!r}")
+        self.reduce = reduce
+        self.include_background, self.square = bool(include_background), bool(square)
+        if class_weight is None:
+            self.class_weight = None
+        else:
+            cw = class_weight.tolist() if isinstance(class_weight, torch.Tensor) else list(class_weight)
+            self.class_weight = tuple(num(f"class_weight[{i}]", v) for i, v in enumerate(cw))
+            if not L.CLASS_MAX_K >= len(self.class_weight) >= 2:
+                raise ValueError(f"MulticlassLoss: class_weight must have 2 .. {L.CLASS_MAX_K} entries, got {len(self.class_weight)}")
+            if any(v < 0 for v in self.class_weight):
+                raise ValueError(f"MulticlassLoss: class_weight must be >= 0, got {class_weight!r}")
+        if output_weights is None:
+            self.output_weights = None
+        elif isinstance(output_weights, dict):
+            self.output_weights = {k: num(f"output_weights[{k!r}]", v) for k, v in output_weights.items()}
+        else:
+            self.output_weights = tuple(num(f"output_weights[{i}]", v) for i, v in enumerate(output_weights))
+        if self.output_weights is not None:
+            vals = self.output_weights.values() if isinstance(self.output_weights, dict) else self.output_weights
+            if any(v < 0 for v in vals):
+                raise ValueError(f"MulticlassLoss: output_weights must be >= 0, got {output_weights!r}")
+        self._plans = {}       # (number of maps, logits shape, device index, main) -> (descriptor, item table, workspace, counts)
+        self._cw_dev = {}      # device index -> the class weights, uploaded once
+        self.counts: Optional[torch.Tensor] = None
+
+    @classmethod
+    def ce_dice(cls, w_ce: float = 0.4, w_dice: float = 0.6, **kw) -> "MulticlassLoss":
+        """the published Swin-UNet / TransUNet loss: ``w_ce * CE + w_dice * Dice`` with squared probabilities in the
+        denominator, ``smooth = 1e-5``, sums over the whole batch"""
+        kw.setdefault("square", True)
+        kw.setdefault("smooth", 1e-5)
+        kw.setdefault("reduce", "batch")
+        return cls(w_ce=w_ce, w_dice=w_dice, **kw)
+
+    # ------------------------------------------------------------------ the containers
+    def weights_for(self, outputs) -> tuple:
+        """the weight of every output map, in the order the model emits them"""
+        keys, maps, _ = _maps_of(outputs)
+        ow = self.output_weights
+        if ow is None:
+            return (1.0,) * len(maps)
+        if isinstance(ow, dict):
+            if keys is None:
+                raise ValueError("MulticlassLoss: output_weights is a dict but the outputs are not")
+            missing = [k for k in keys if k not in ow]
+            if missing:
+                raise ValueError(f"MulticlassLoss: output_weights has no entry for the outputs {missing}")
+            return tuple(ow[k] for k in keys)
+        if len(ow) != len(maps):
+            raise ValueError(f"MulticlassLoss: {len(ow)} output_weights for {len(maps)} output maps")
+        return ow
+
+    def _plan(self, n_items: int, shape, device: torch.device, main: int):
+        key = (n_items, tuple(shape), device.index, main)
+        plan = self._plans.get(key)
+        if plan is None:
+            N, K = int(shape[0]), int(shape[1])
+            hw = 1
+            for s in shape[2:]:
+                hw *= int(s)
+            desc = L.ClassDesc(n_items, N, K, hw, self.w_ce, self.w_dice, self.smooth, self.label_smoothing, self.ignore_index,
+                               _CLASS_REDUCES[self.reduce], int(self.include_background), int(self.square), main)
+            ws = torch.empty((L.class_loss_workspace_bytes(desc) + 7) // 8, dtype=torch.float64, device=device)
+            counts = torch.zeros(K + 1, 3, dtype=torch.int64, device=device)
+            plan = self._plans[key] = (desc, (L.ClassItem * n_items)(), ws, counts)
+        return plan
+
+    def _weights_on(self, device: torch.device, K: int):
+        if self.class_weight is None:
+            return None
+        if len(self.class_weight) != K:
+            raise ValueError(f"MulticlassLoss: {len(self.class_weight)} class_weight entries for logits of {K} classes")
+        cw = self._cw_dev.get(device.index)
+        if cw is None:
+            cw = self._cw_dev[device.index] = torch.tensor(self.class_weight, dtype=torch.float32, device=device)
+        return cw
+
+    def _launch(self, logits, target: torch.Tensor, weights, main: int, need):
+        """one uz_class_loss over all maps -> (loss, dice, [d(loss)/d(map) in fp32, or None where need is False])"""
+        if not logits:
+            raise ValueError("MulticlassLoss: no output map")
+        if len(logits) > L.CLASS_MAX_ITEMS:
+            raise ValueError(f"MulticlassLoss: {len(logits)} output maps, at most {L.CLASS_MAX_ITEMS} per call")
+        if target.dtype not in _INT_DTYPES:
+            raise ValueError(f"MulticlassLoss: the target holds class indices and must have an integer dtype, got {target.dtype}")
+        shape = tuple(logits[0].shape)
+        if len(shape) < 3:
+            raise ValueError(f"MulticlassLoss: logits must be (N, K, H, W), got shape {shape}")
+        K = shape[1]
+        if not 2 <= K <= L.CLASS_MAX_K:
+            raise ValueError(f"MulticlassLoss: K = {K} classes outside [2, {L.CLASS_MAX_K}]")
+        want = (shape[0],) + shape[2:]
+        tshape = tuple(target.shape)
+        if tshape == (shape[0], 1) + shape[2:]:
+            tshape = want
+        if tshape != want:
+            raise ValueError(f"MulticlassLoss: logits of shape {shape} against a target of shape {tuple(target.shape)}; "
+                             f"expected {want} or {(shape[0], 1) + shape[2:]}")
+        for v in logits:
+            if tuple(v.shape) != shape:
+                raise ValueError(f"MulticlassLoss: output maps of shape {tuple(v.shape)} and {shape} in one call")
+            if v.dtype not in (torch.float32, torch.bfloat16):
+                raise ValueError(f"MulticlassLoss: logits must be float32 or bfloat16, got {v.dtype}")
+        if target.numel() == 0:
+            raise ValueError("MulticlassLoss: empty maps")
+        L.require_cuda(target, *logits)
+        for v in logits:
+            if v.device != target.device:
+                raise ValueError(f"MulticlassLoss: an output map on {v.device} against a target on {target.device}")
+        xs = [v.detach().contiguous().float() for v in logits]     # bf16 logits become fp32, as in RegionLoss
+        y = target.detach().reshape(want).contiguous().to(torch.int32)
+        cw = self._weights_on(y.device, K)
+        desc, items, ws, counts = self._plan(len(xs), shape, y.device, main)
+        dl = [torch.empty_like(x) if g else None for x, g in zip(xs, need)]
+        out = torch.empty(2, dtype=torch.float32, device=y.device)
+        for it, x, d, w in zip(items, xs, dl, weights):
+            it.logits, it.dlogits, it.weight = x.data_ptr(), (d.data_ptr() if d is not None else None), w
+        L.class_loss(desc, items, y, cw, out, counts, ws)
+        self.counts = counts
+        return out[0], out[1], dl
+
+    # ------------------------------------------------------------------ the three forms
+    def loss_and_dice(self, outputs, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(loss, Dice metric of the main output) as 0-dim device tensors; the loss is differentiable with respect to every
+        output tensor through ONE autograd node (any CUDA fp32 / bf16 logits: a stock torch model's too)"""
+        _, maps, main = _maps_of(outputs)
+        return _MulticlassFn.apply(self, target, self.weights_for(outputs), main, *maps)
+
+    def __call__(self, outputs, target: torch.Tensor) -> torch.Tensor:
+        return self.loss_and_dice(outputs, target)[0]
+
+    def direct(self, outputs, target: torch.Tensor):
+        """(loss, dice, d(loss)/d(outputs)) without an autograd node -- the graphed step's form; the gradients (fp32) come in
+        the order the model emits its outputs"""
+        _, maps, main = _maps_of(outputs)
+        loss, dice, dl = self._launch(maps, target, self.weights_for(outputs), main, (True,) * len(maps))
+        return loss, dice, tuple(dl)
+
+    def __repr__(self) -> str:
+        return (f"MulticlassLoss(w_ce={self.w_ce}, w_dice={self.w_dice}, smooth={self.smooth}, "
+                f"label_smoothing={self.label_smoothing}, class_weight={self.class_weight}, ignore_index={self.ignore_index}, "
+                f"include_background={self.include_background}, reduce={self.reduce!r}, square={self.square}, "
                 f"output_weights={self.output_weights})")

@@ -26,7 +26,9 @@ them in place, so read (``.item()``) or ``.clone()`` what must outlive the step.
 Loss: the default ``criterion="bce_dice"`` is the fused kernel of ``loss.py`` (BCEWithLogits + its gradient + the
 Dice metric, one pass) inside the first graph.  A ``loss.RegionLoss`` instance (BCE + soft Dice / Tversky / focal Tversky,
 weighted over the output maps) sits in the same place: three launches inside the first graph, ``step.dice`` keeps its
-meaning; with several ranks each rank evaluates it on its own shard, so ``reduce="batch"`` is per shard.  Any other
+meaning; with several ranks each rank evaluates it on its own shard, so ``reduce="batch"`` is per shard.  A
+``loss.MulticlassLoss`` instance (softmax cross-entropy + Dice over class-index labels) sits there too; the static target
+buffer is then int32 (the criterion's ``target_dtype``), float32 for every other criterion.  Any other
 callable ``criterion(outputs, target) -> loss`` works too; it is evaluated EAGERLY between the forward graph and the
 backward graphs, because library reductions must not be captured on this stack: a memset node of a replayed hipGraph writes its value only in the first replay, and torch's multi-block
 reductions reset their semaphores with exactly such a node (tools/graph_canary.py).
@@ -40,7 +42,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from .graph import HipModule, PhasedStep
-from .loss import RegionLoss, loss_and_dice, loss_and_dice_direct
+from .loss import MulticlassLoss, RegionLoss, loss_and_dice, loss_and_dice_direct
 from .optim import FlatClipAdamW
 
 # hipGraph capture checks only THIS thread's calls: the process-group watchdog thread polls its events concurrently
@@ -111,7 +113,7 @@ class _ShapeGraphs:
 
 
 class GraphedStep:
-    def __init__(self, model: nn.Module, criterion: Union[str, RegionLoss, Callable] = "bce_dice", *, lr: float = 1e-4,
+    def __init__(self, model: nn.Module, criterion: Union[str, RegionLoss, MulticlassLoss, Callable] = "bce_dice", *, lr: float = 1e-4,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-5,
                  max_norm: float = 1.0, phases: int = 5, process_group=None, data_parallel: Optional[bool] = None,
                  cu_reserve: Optional[int] = None, comm: str = "overlap", comm_dtype: Optional[torch.dtype] = None):
@@ -141,13 +143,15 @@ class GraphedStep:
             self._fused_loss = True
             self._loss_fn = lambda out, t: loss_and_dice(out, t)[0]
             self._fused = (loss_and_dice, loss_and_dice_direct)
-        elif isinstance(criterion, RegionLoss):      # fused too: uz_region_loss, graph-safe, hands over its own gradients
+        elif isinstance(criterion, (RegionLoss, MulticlassLoss)):      # fused too: uz_region_loss / uz_class_loss, graph-safe, hand over their own gradients
             self._fused_loss = True
             self._loss_fn = lambda out, t: criterion.loss_and_dice(out, t)[0]
             self._fused = (criterion.loss_and_dice, criterion.direct)
         else:
             self._fused_loss = False
             self._loss_fn = criterion
+        # the static target buffer: float32 masks, or what the criterion asks for (MulticlassLoss: int32 class indices)
+        self._target_dtype = getattr(criterion, "target_dtype", torch.float32)
         self.lr, self.betas, self.eps, self.weight_decay, self.max_norm = lr, betas, eps, weight_decay, max_norm
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
@@ -375,10 +379,11 @@ class GraphedStep:
         g = self._graphs.get(key)
         if g is None:
             # static input buffers of this shape (fp32 on the model's device, what `.float().to(device)` of
-            # training_loop.py:109-110 produces); later calls copy into them -- host tensors included
+            # training_loop.py:109-110 produces; the target in the criterion's target_dtype where it names one); later calls
+            # copy into them -- host tensors included
             dev = next(self.model.parameters()).device
             sx = x.detach().to(device=dev, dtype=torch.float32, copy=True)
-            st = target.detach().to(device=dev, dtype=torch.float32, copy=True)
+            st = target.detach().to(device=dev, dtype=self._target_dtype, copy=True)
             if self.opt is None:
                 self._setup(sx, st)
             g = self._graphs[key] = self._capture(sx, st)
