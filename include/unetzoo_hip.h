@@ -1022,6 +1022,49 @@ int uz_bn_elu_bwd_apply(const uz_bn_elu_bwd_desc* d, const void* x, const void* 
                         const void* g2, const float* mask2, const float* scale, const float* shift, const float* mean,
                         const float* invstd, const double* sums, void* dx, void* gres, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Training-time augmentation on the device: flips, rotation, scaling, translation, an optional smooth displacement
+ * grid and an intensity jitter, for the picture and its mask together.  uz_augment.hip
+ * uz_augment_params (one tiny launch): u (N, 8) fp32 uniforms in [0, 1) -> params (N, 16) fp32 per sample,
+ *   [a, b, ox, c, d, oy, contrast, brightness, 0 ...]:
+ *   fx = u0 < p_hflip ? -1 : 1, fy = u1 < p_vflip ? -1 : 1, theta = (2 u2 - 1) rotate (degrees),
+ *   s = scale_min + u3 (scale_max - scale_min), tx = (2 u4 - 1) translate W, ty = (2 u5 - 1) translate H,
+ *   brightness = (2 u6 - 1) brightness_range, contrast = 1 + (2 u7 - 1) contrast_range;
+ *   the inverse map M = (1 / s) R(-theta) diag(fx, fy): a = cos fx / s, b = sin fy / s, c = -sin fx / s, d = cos fy / s,
+ *   ox = W / 2 + tx - 0.5, oy = H / 2 + ty - 0.5.  Formed in float64, rounded once.
+ * uz_augment_apply (one launch): image (N, C, H, W) fp32, C in 1..4; mask (mask_kind) none, fp32 (N, Cm, H, W) with Cm in
+ *   1..8, or int32 (N, H, W); disp (nullable, G = 0) the displacement grid (N, 2, G, G) fp32 in pixels (x then y), G in
+ *   2..16.  Output pixel (i, j), u = j + 0.5 - W / 2, v = i + 0.5 - H / 2, reads the source at
+ *     sx = a u + b v + ox + Dx(i, j),  sy = c u + d v + oy + Dy(i, j)         (pixel indices: sx = 3 is column 3)
+ *   D = the grid interpolated bilinearly at (j (G - 1) / (W - 1), i (G - 1) / (H - 1))  (align_corners = True).
+ *   image_out = contrast * B + brightness, B = bilinear over the four taps around (floor sx, floor sy), a tap outside the
+ *   picture contributing image_fill; mask_out = the mask at (floor(sx + 0.5), floor(sy + 0.5)), mask_fill / label_fill
+ *   outside, no jitter.  The outputs have the inputs' shapes and must not overlap any input or each other.
+ * A thread owns four consecutive pixels of one row for every plane: 16-byte stores when W % 4 == 0 and the outputs are
+ * 16-byte aligned, 4-byte stores of the same values otherwise.  uz_augment_grid() returns the number of workgroups of the
+ * launch and (units, nullable) the units they share out (a unit: 256 consecutive runs of four pixels of one sample):
+ * units > workgroups means workgroups walk.
+ * UZ_EINVAL before any launch: null descriptor / pointer, a mask or grid pointer that does not match mask_kind / G,
+ * N, H, W <= 0, C outside 1..4, Cm outside 1..8, G outside {0, 2..16} (or H, W < 2 with a grid), non-finite fills,
+ * N max(C, Cm) H W >= 2^31, H W >= 2^30, overlapping or misaligned (4 bytes) tensors; uz_augment_params: probabilities outside [0, 1], scale not
+ * 0 < min <= max, a negative or non-finite range. */
+#define UZ_AUGMENT_MASK_NONE 0
+#define UZ_AUGMENT_MASK_F32 1
+#define UZ_AUGMENT_MASK_I32 2
+typedef struct uz_augment_desc {
+  int N, C, H, W;
+  int mask_kind; /* UZ_AUGMENT_MASK_* */
+  int Cm;        /* channels of an fp32 mask */
+  int G;         /* 0: no displacement grid */
+  float p_hflip, p_vflip, rotate, scale_min, scale_max, translate, brightness, contrast;
+  float image_fill, mask_fill;
+  int label_fill;
+} uz_augment_desc;
+int uz_augment_params(const uz_augment_desc* d, const float* u, float* params, void* stream);
+int uz_augment_grid(const uz_augment_desc* d, int* units /* nullable */);
+int uz_augment_apply(const uz_augment_desc* d, const float* image, const void* mask, const float* params, const float* disp,
+                     float* image_out, void* mask_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

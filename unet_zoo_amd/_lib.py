@@ -56,6 +56,7 @@ EXPORTS = (
     "uz_conv_igemm_bnact_supported", "uz_conv_igemm_bnact", "uz_conv3x3_first_fwd_bnact",
     "uz_region_loss_workspace_bytes", "uz_region_loss",
     "uz_class_loss_workspace_bytes", "uz_class_loss",
+    "uz_augment_params", "uz_augment_grid", "uz_augment_apply",
 )
 
 
@@ -174,6 +175,17 @@ class ClassDesc(Structure):
     _fields_ = [("n_items", c_int), ("N", c_int), ("K", c_int), ("HW", ctypes.c_longlong)] \
         + [(n, c_float) for n in ("w_ce", "w_dice", "smooth", "label_smoothing")] \
         + [(n, c_int) for n in ("ignore_index", "reduce", "include_background", "square", "metric_item")]
+
+
+AUGMENT_MASK_NONE, AUGMENT_MASK_F32, AUGMENT_MASK_I32 = 0, 1, 2
+
+
+class AugmentDesc(Structure):
+    """uz_augment_desc"""
+    _fields_ = [(n, c_int) for n in ("N", "C", "H", "W", "mask_kind", "Cm", "G")] \
+        + [(n, c_float) for n in ("p_hflip", "p_vflip", "rotate", "scale_min", "scale_max", "translate", "brightness",
+                                  "contrast", "image_fill", "mask_fill")] \
+        + [("label_fill", c_int)]
 
 
 class HipLibraryError(RuntimeError):
@@ -358,6 +370,9 @@ def load():
     lib.uz_region_loss.argtypes = [POINTER(RegionDesc), POINTER(RegionItem), vp, vp, vp]
     lib.uz_class_loss_workspace_bytes.argtypes = [POINTER(ClassDesc)]
     lib.uz_class_loss.argtypes = [POINTER(ClassDesc), POINTER(ClassItem), vp, vp, vp, vp, vp, vp]
+    lib.uz_augment_params.argtypes = [POINTER(AugmentDesc), vp, vp, vp]
+    lib.uz_augment_grid.argtypes = [POINTER(AugmentDesc), POINTER(c_int)]
+    lib.uz_augment_apply.argtypes = [POINTER(AugmentDesc), vp, vp, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("uz_last_error_string", "uz_source_hash"):

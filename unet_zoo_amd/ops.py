@@ -1637,3 +1637,35 @@ def bn_elu_bwd(x: Act, vec: torch.Tensor, out: Act, g0: Act, g1: Optional[Act], 
     with _Timed("bn_elu_bwd_apply", 0.0, es * x.P * x.C * (nsrc + 1 + (gres is not None))):
         L.check(lib.uz_bn_elu_bwd_apply(byref(d), *args, sums.data_ptr(), dx.ptr(), gres.ptr() if gres is not None else None, s),
                 "uz_bn_elu_bwd_apply")
+
+
+# ---- GpuAugment: the per-sample warp + jitter of picture and mask (uz_augment.hip) ------------------------------------------
+def augment_params(desc: "L.AugmentDesc", u: torch.Tensor, params: torch.Tensor) -> None:
+    """params (N, 16) fp32 <- the inverse map and the jitter of every sample from u (N, 8) fp32 uniforms in [0, 1)"""
+    L.require_cuda(u, params)
+    assert u.dtype == params.dtype == torch.float32 and u.is_contiguous() and params.is_contiguous()
+    assert tuple(u.shape) == (desc.N, 8) and tuple(params.shape) == (desc.N, 16)
+    with _Timed("augment_params", 0.0, 96.0 * desc.N):
+        L.check(L.load().uz_augment_params(byref(desc), u.data_ptr(), params.data_ptr(), L.stream_ptr()), "uz_augment_params")
+
+
+def augment_grid(desc: "L.AugmentDesc") -> tuple:
+    """(workgroups, units) of the uz_augment_apply launch for this descriptor: units > workgroups means workgroups walk"""
+    units = ctypes.c_int(0)
+    grid = L.check_count(L.load().uz_augment_grid(byref(desc), byref(units)), "uz_augment_grid")
+    return grid, units.value
+
+
+def augment_apply(desc: "L.AugmentDesc", image: torch.Tensor, mask: Optional[torch.Tensor], params: torch.Tensor,
+                  disp: Optional[torch.Tensor], image_out: torch.Tensor, mask_out: Optional[torch.Tensor]) -> None:
+    """image_out, mask_out <- image (N, C, H, W) fp32 and mask (fp32 (N, Cm, H, W) or int32 (N, H, W)) read through each
+    sample's map in `params` and the displacement grid disp (N, 2, G, G); one launch"""
+    L.require_cuda(image, mask, params, disp, image_out, mask_out)
+    for t in (image, mask, params, disp, image_out, mask_out):
+        assert t is None or t.is_contiguous()
+    assert image.dtype == image_out.dtype == params.dtype == torch.float32 and image_out.shape == image.shape
+    assert (mask is None) == (mask_out is None) and (mask is None or (mask.dtype == mask_out.dtype and mask.shape == mask_out.shape))
+    nb = 2.0 * 4 * (image.numel() + (mask.numel() if mask is not None else 0))
+    with _Timed("augment_apply", 0.0, nb):
+        L.check(L.load().uz_augment_apply(byref(desc), image.data_ptr(), _p(mask), params.data_ptr(), _p(disp),
+                                          image_out.data_ptr(), _p(mask_out), L.stream_ptr()), "uz_augment_apply")

@@ -32,6 +32,13 @@ buffer is then int32 (the criterion's ``target_dtype``), float32 for every other
 callable ``criterion(outputs, target) -> loss`` works too; it is evaluated EAGERLY between the forward graph and the
 backward graphs, because library reductions must not be captured on this stack: a memset node of a replayed hipGraph writes its value only in the first replay, and torch's multi-block
 reductions reset their semaphores with exactly such a node (tools/graph_canary.py).
+
+Augmentation: ``GraphedStep(model, augment=unet_zoo_amd.GpuAugment(...))`` copies the caller's batch into static RAW buffers and
+captures the augmentation's two launches (``uz_augment.hip``) at the head of the first graph -- the forward graph on the eager-
+criterion route, phase 0 on the fused-loss route; the model and the criterion read the augmentation's static outputs
+(``step.augmented``).  Its draws are torch's generator's, so every replay draws afresh and a seed reproduces a run; with several
+ranks each rank draws from its OWN generator (seed the ranks differently unless they are meant to augment alike).  Without
+``augment`` nothing changes: the same graphs, the same buffers, the same numbers.
 """
 from __future__ import annotations
 
@@ -42,6 +49,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from .graph import HipModule, PhasedStep
+from .augment import GpuAugment
 from .loss import MulticlassLoss, RegionLoss, loss_and_dice, loss_and_dice_direct
 from .optim import FlatClipAdamW
 
@@ -108,16 +116,20 @@ def _unwrap(model: nn.Module) -> HipModule:
 
 
 class _ShapeGraphs:
-    """everything captured for one (input shape, target shape)"""
-    __slots__ = ("x", "t", "fwd", "phases", "gouts", "loss", "dice", "outputs", "pool", "ps")
+    """everything captured for one (input shape, target shape): x / t take the caller's batch, mx / mt are what the model and
+    the criterion read -- the same tensors, or the static outputs of the augmentation `aug` captured in front of the model"""
+    __slots__ = ("x", "t", "mx", "mt", "aug", "fwd", "phases", "gouts", "loss", "dice", "outputs", "pool", "ps")
 
 
 class GraphedStep:
     def __init__(self, model: nn.Module, criterion: Union[str, RegionLoss, MulticlassLoss, Callable] = "bce_dice", *, lr: float = 1e-4,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-5,
                  max_norm: float = 1.0, phases: int = 5, process_group=None, data_parallel: Optional[bool] = None,
-                 cu_reserve: Optional[int] = None, comm: str = "overlap", comm_dtype: Optional[torch.dtype] = None):
-        """comm: when the gradient exchange of a data-parallel step runs -- "overlap": the span of every finished backward
+                 cu_reserve: Optional[int] = None, comm: str = "overlap", comm_dtype: Optional[torch.dtype] = None,
+                 augment: Optional[GpuAugment] = None):
+        """augment: a GpuAugment applied to every batch inside the first graph (module docstring); every rank draws from its own
+        generator.
+        comm: when the gradient exchange of a data-parallel step runs -- "overlap": the span of every finished backward
         phase is all-reduced while the next phase's graph runs; "tail": ONE all-reduce of the whole flat buffer after the
         last phase.  The same graphs serve both; autotune_comm() times them on the job's own hardware and keeps the faster
         one (the persistent one-workgroup-per-CU grids and a collective's kernels compete for CUs: which schedule wins
@@ -152,6 +164,9 @@ class GraphedStep:
             self._loss_fn = criterion
         # the static target buffer: float32 masks, or what the criterion asks for (MulticlassLoss: int32 class indices)
         self._target_dtype = getattr(criterion, "target_dtype", torch.float32)
+        if augment is not None and not isinstance(augment, GpuAugment):
+            raise TypeError(f"augment must be a unet_zoo_amd.GpuAugment, got {type(augment).__name__}")
+        self.augment = augment
         self.lr, self.betas, self.eps, self.weight_decay, self.max_norm = lr, betas, eps, weight_decay, max_norm
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
@@ -253,9 +268,11 @@ class GraphedStep:
             torch.cuda.synchronize()
             self._capture_opt()
 
-    def _capture(self, x: torch.Tensor, t: torch.Tensor) -> _ShapeGraphs:
+    def _capture(self, x: torch.Tensor, t: torch.Tensor, aug=None) -> _ShapeGraphs:
+        """x, t: the static tensors the model and the criterion read; aug: the bound augmentation that writes them (its two
+        launches open the first graph) or None"""
         g = _ShapeGraphs()
-        g.x, g.t = x, t
+        g.x, g.t, g.mx, g.mt, g.aug = x, t, x, t, aug
         ps = PhasedStep(self.model, self._loss_fn)
         cuts = self._cuts
         g.phases, g.fwd, g.gouts, g.dice, pool = [], None, None, None, None
@@ -280,7 +297,9 @@ class GraphedStep:
             # d(loss)/d(output) buffers
             g.fwd = _new_graph()
             with torch.cuda.graph(g.fwd, capture_error_mode=CAPTURE_MODE):
-                ps.emit(g.x)
+                if aug is not None:
+                    aug.run()
+                ps.emit(g.mx)
             _check_capture(g.fwd, "forward graph")
             pool = g.fwd.pool()
             g.outputs = ps.outputs
@@ -290,7 +309,9 @@ class GraphedStep:
             gk = _new_graph()
             with torch.cuda.graph(gk, pool=pool, capture_error_mode=CAPTURE_MODE):
                 if k == 0 and self._fused_loss:
-                    g.loss = ps.forward(g.x, g.t)
+                    if aug is not None:
+                        aug.run()
+                    g.loss = ps.forward(g.mx, g.mt)
                     g.outputs = ps.outputs
                     g.dice = dice_box[-1].detach()
                 ps.backward(cuts[k], cuts[k + 1], k == 0)
@@ -384,9 +405,19 @@ class GraphedStep:
             dev = next(self.model.parameters()).device
             sx = x.detach().to(device=dev, dtype=torch.float32, copy=True)
             st = target.detach().to(device=dev, dtype=self._target_dtype, copy=True)
+            aug, mx, mt = None, sx, st
+            if self.augment is not None:
+                # the augmentation reads the raw copies and writes static outputs of its own; for the dry run they hold the
+                # raw batch (nothing is drawn before the capture, the generator is where the caller left it)
+                sx, st = sx.contiguous(), st.contiguous()      # bind() reads these very tensors in place
+                aug = self.augment.bind(sx, st)
+                mx, mt = aug.out_image, aug.out_mask
+                mx.copy_(sx)
+                mt.copy_(st)
             if self.opt is None:
-                self._setup(sx, st)
-            g = self._graphs[key] = self._capture(sx, st)
+                self._setup(mx, mt)
+            g = self._graphs[key] = self._capture(mx, mt, aug)
+            g.x, g.t = sx, st
         self._cur = g
         if x.data_ptr() != g.x.data_ptr():
             g.x.copy_(x)
@@ -394,7 +425,7 @@ class GraphedStep:
             g.t.copy_(target)
         if g.fwd is not None:
             g.fwd.replay()
-            loss = g.ps.loss(g.t)                    # eager criterion; leaves d(loss)/d(output)
+            loss = g.ps.loss(g.mt)                   # eager criterion; leaves d(loss)/d(output)
             for dst, src in zip(g.gouts, g.ps._gouts):
                 if src is None:
                     dst.zero_()
@@ -468,6 +499,12 @@ class GraphedStep:
         return self.opt.last_grad_norm()
 
     @property
+    def augmented(self) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+        """(pictures, masks) the last step trained on: the augmentation's STATIC outputs (None without `augment`)"""
+        g = self._cur
+        return None if g is None or g.aug is None else (g.aug.out_image, g.aug.out_mask)
+
+    @property
     def flat_grad(self) -> torch.Tensor:
         return self.opt.flat_g[:self.opt.n]
 
@@ -476,6 +513,8 @@ class GraphedStep:
         k = len(self._cuts) - 1 if self._cuts else self.n_phases
         opt = "hipGraph(clip+AdamW on flat buffers, 3 launches)"
         crit = "" if self._fused_loss else "hipGraph(fwd) + eager criterion + "
+        if self.augment is not None:
+            crit = "GpuAugment at the head of the first hipGraph + " + crit
         if not self.distributed:
             return f"{crit}hipGraph({'fwd+' if self._fused_loss else ''}bwd) + {opt}"
         mb = [round((a1 - a0) * 4 / 2 ** 20, 1) for a0, a1 in self._spans]
