@@ -1065,6 +1065,49 @@ int uz_augment_grid(const uz_augment_desc* d, int* units /* nullable */);
 int uz_augment_apply(const uz_augment_desc* d, const float* image, const void* mask, const float* params, const float* disp,
                      float* image_out, void* mask_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Surface-distance metrics of a thresholded prediction A against its target B, per (image, class) pair, exact: Hausdorff,
+ * percentile Hausdorff (HD95) and average symmetric surface distance as medpy's hd / hd95 / assd compute them in 2D with
+ * connectivity 1.  uz_surface.hip
+ *   S(X)  = the pixels of X with a 4-neighbour outside X; outside the picture counts as outside X
+ *   d2(p, S) = min over s in S of (pi - si)^2 + (pj - sj)^2, an integer
+ *   D     = { d2(p, S(B)) : p in S(A) } + { d2(p, S(A)) : p in S(B) } as a multiset, n = |S(A)| + |S(B)|
+ *   hd    = spacing sqrt(max D)
+ *   hdq   = spacing (lo + f (hi - lo)),  r = (n - 1) (q / 100), k = floor(r), f = r - k, lo = sqrt(D_(k)),
+ *           hi = sqrt(D_(min(k + 1, n - 1))), D_(k) the k-th smallest (from 0): numpy.percentile(sqrt(D), q), linear
+ *   assd  = spacing / 2 (mean of sqrt over the first part of D + mean of sqrt over the second)
+ *   state = 0 both masks non-empty, 1 A empty, 2 B empty, 3 both empty; with a state other than 0 the three values and the
+ *           three d2 statistics are 0
+ * The order statistics are exact (integer histograms of d2); sqrt, the interpolation and the sums are float64, the sums in
+ * a fixed order, and every value is rounded to float32 once.
+ * UZ_SURFACE_BINARY: logits and target (N, C, H, W) fp32; A = logits > 0, B = target > 0.5, every channel a pair: P = C.
+ * UZ_SURFACE_CLASS : logits (N, C, H, W) fp32 with C = K classes, target (N, H, W) int32 labels; A = (argmax_K == c), ties
+ *   to the lowest index, B = (label == c), for c = first_class .. K - 1: P = K - first_class.  A pixel whose label is
+ *   ignore_index or outside [0, K) belongs to no mask of any class.
+ * out (N, P, 4) fp32 = hd, hdq, assd, 0;  stats (N, P, 8) int64 = |S(A)|, |S(B)|, max d2, D_(k), D_(k+1), state, |A|, |B|.
+ * One call is SEVEN launches whatever the shape (clear, codes, rows, columns, select1, level2, finalize), no allocation, no
+ * memset, no host synchronisation; the workspace (uz_surface_workspace_bytes, 16-byte aligned) is cleared by the first
+ * launch.  uz_surface_grid() returns the workgroups of the widest launch (the column pass) and (units, nullable) the units
+ * they share out (a unit: 256 consecutive pixels of one mask of one pair): units > workgroups means workgroups walk.
+ * UZ_EINVAL before any launch: null descriptor / pointer, unknown mode, N, C, H or W < 1, H or W > 4096, in the class mode
+ * K outside [2, UZ_CLASS_MAX_K] or first_class outside [0, K), q outside (0, 100], spacing not positive and finite,
+ * N C H W >= 2^31, tensors misaligned (4 bytes; stats 8, workspace 16) or overlapping. */
+#define UZ_SURFACE_BINARY 0
+#define UZ_SURFACE_CLASS 1
+typedef struct uz_surface_desc {
+  int mode;         /* UZ_SURFACE_* */
+  int N, C, H, W;   /* C: channels (binary) or classes K (class mode) */
+  int first_class;  /* class mode: the first class that is a pair (1 leaves the background out) */
+  int ignore_index; /* class mode */
+  int reserved;
+  double q;         /* percentile of hdq, 0 < q <= 100 */
+  double spacing;   /* isotropic pixel spacing */
+} uz_surface_desc;
+long long uz_surface_workspace_bytes(const uz_surface_desc* d); /* < 0: refused */
+int uz_surface_grid(const uz_surface_desc* d, int* units /* nullable */);
+int uz_surface_metrics(const uz_surface_desc* d, const float* logits, const void* target, float* out, long long* stats,
+                       void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

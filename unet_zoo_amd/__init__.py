@@ -10,8 +10,10 @@ from .step import GraphedStep
 from .evalstep import GraphedEval
 from .loss import MulticlassLoss, RegionLoss
 from .augment import GpuAugment
+from .surface import SurfaceMetrics
 from .config import Config, load_config
 
 __version__ = "0.1.0"
 __all__ = ["create_model", "list_models", "get_model_config", "hip_models", "set_default_dtype",
-           "get_default_dtype", "GraphedStep", "GraphedEval", "RegionLoss", "MulticlassLoss", "GpuAugment", "Config", "load_config"]
+           "get_default_dtype", "GraphedStep", "GraphedEval", "RegionLoss", "MulticlassLoss", "GpuAugment", "SurfaceMetrics",
+           "Config", "load_config"]

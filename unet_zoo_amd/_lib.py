@@ -57,6 +57,7 @@ EXPORTS = (
     "uz_region_loss_workspace_bytes", "uz_region_loss",
     "uz_class_loss_workspace_bytes", "uz_class_loss",
     "uz_augment_params", "uz_augment_grid", "uz_augment_apply",
+    "uz_surface_workspace_bytes", "uz_surface_grid", "uz_surface_metrics",
 )
 
 
@@ -186,6 +187,16 @@ class AugmentDesc(Structure):
         + [(n, c_float) for n in ("p_hflip", "p_vflip", "rotate", "scale_min", "scale_max", "translate", "brightness",
                                   "contrast", "image_fill", "mask_fill")] \
         + [("label_fill", c_int)]
+
+
+SURFACE_BINARY, SURFACE_CLASS = 0, 1
+SURFACE_MAX_HW = 4096
+
+
+class SurfaceDesc(Structure):
+    """uz_surface_desc"""
+    _fields_ = [(n, c_int) for n in ("mode", "N", "C", "H", "W", "first_class", "ignore_index", "reserved")] \
+        + [("q", c_double), ("spacing", c_double)]
 
 
 class HipLibraryError(RuntimeError):
@@ -373,6 +384,9 @@ def load():
     lib.uz_augment_params.argtypes = [POINTER(AugmentDesc), vp, vp, vp]
     lib.uz_augment_grid.argtypes = [POINTER(AugmentDesc), POINTER(c_int)]
     lib.uz_augment_apply.argtypes = [POINTER(AugmentDesc), vp, vp, vp, vp, vp, vp, vp]
+    lib.uz_surface_workspace_bytes.argtypes = [POINTER(SurfaceDesc)]
+    lib.uz_surface_grid.argtypes = [POINTER(SurfaceDesc), POINTER(c_int)]
+    lib.uz_surface_metrics.argtypes = [POINTER(SurfaceDesc), vp, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("uz_last_error_string", "uz_source_hash"):
@@ -427,6 +441,25 @@ def class_loss(desc: "ClassDesc", items, labels: torch.Tensor, class_weight, out
                                class_weight.data_ptr() if class_weight is not None else None, out2.data_ptr(),
                                counts.data_ptr() if counts is not None else None, workspace.data_ptr(), stream_ptr()),
           "uz_class_loss")
+
+
+def surface_workspace_bytes(desc: "SurfaceDesc") -> int:
+    """uz_surface_workspace_bytes(): bytes of workspace a uz_surface_metrics call with this descriptor needs"""
+    return check_count(load().uz_surface_workspace_bytes(ctypes.byref(desc)), "uz_surface_workspace_bytes")
+
+
+def surface_grid(desc: "SurfaceDesc") -> tuple:
+    """uz_surface_grid(): (workgroups, units) of the widest launch of uz_surface_metrics for this descriptor"""
+    units = c_int(0)
+    grid = check_count(load().uz_surface_grid(ctypes.byref(desc), ctypes.byref(units)), "uz_surface_grid")
+    return grid, units.value
+
+
+def surface_metrics(desc: "SurfaceDesc", logits: torch.Tensor, target: torch.Tensor, out: torch.Tensor, stats: torch.Tensor,
+                    workspace: torch.Tensor) -> None:
+    """uz_surface_metrics() on the current stream: seven launches, no allocation, no host read"""
+    check(load().uz_surface_metrics(ctypes.byref(desc), logits.data_ptr(), target.data_ptr(), out.data_ptr(), stats.data_ptr(),
+                                    workspace.data_ptr(), stream_ptr()), "uz_surface_metrics")
 
 
 def set_cu_reserve(n: int) -> None:

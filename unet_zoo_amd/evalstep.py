@@ -13,6 +13,11 @@ replayed:
     loss, dice = ev(images, masks)                 # 0-dim device tensors, no host sync; ev.outputs = the model's outputs
     mean_loss, mean_dice = ev.evaluate(loader)     # validate_one_epoch: per-batch means, ONE read-back at the end
 
+``surface=SurfaceMetrics(...)`` adds the boundary distances of the main output map (Hausdorff, HD95, ASSD: surface.py) to the
+captured graph, after the loss: ``ev.surface`` is its static ``(out, stats)`` after each call, and ``evaluate`` sums the three
+values over the valid (image, pair) occurrences and counts the four states on the device, read back with the two means in the
+same single read-back: ``ev.surface_summary``.  Without ``surface`` the graph and every result are unchanged.
+
 ``fold_bn=True`` runs this object's captures on engines with ``fold_bn_eval`` set: a Conv -> BatchNorm -> ReLU layer without pool or
 residual becomes one launch whose epilogue forms the activation from the convolution's fp32 result and the running-statistics
 (scale, shift) -- the raw output is neither written nor re-read.  fp32 results are bit-identical to the eager forward; bf16
@@ -42,16 +47,23 @@ from . import _lib as L
 from .engine import Engine
 from .loss import MulticlassLoss, RegionLoss, loss_and_dice
 from .step import CAPTURE_MODE, _check_capture, _new_graph, _unwrap
+from .surface import SurfaceMetrics
 
 
 class _EvalGraph:
     """everything captured for one (input shape, target shape)"""
-    __slots__ = ("x", "t", "graph", "outputs", "loss", "dice", "folded", "unfolded")
+    __slots__ = ("x", "t", "graph", "outputs", "loss", "dice", "folded", "unfolded", "surface")
 
 
 class GraphedEval:
-    def __init__(self, model: nn.Module, criterion: Union[str, RegionLoss, MulticlassLoss, Callable] = "bce_dice", *, fold_bn: bool = False):
+    def __init__(self, model: nn.Module, criterion: Union[str, RegionLoss, MulticlassLoss, Callable] = "bce_dice", *, fold_bn: bool = False,
+                 surface: Optional[SurfaceMetrics] = None):
         self.model = _unwrap(model)
+        if surface is not None and not isinstance(surface, SurfaceMetrics):
+            raise TypeError(f"GraphedEval: surface must be a SurfaceMetrics object or None, got {type(surface).__name__}")
+        self._surface = surface
+        self.surface: Optional[Tuple[torch.Tensor, torch.Tensor]] = None      # the static (out, stats) of the last call
+        self.surface_summary: Optional[dict] = None                             # of the last evaluate()
         if isinstance(criterion, str):
             if criterion != "bce_dice":
                 raise ValueError(f"unknown built-in criterion {criterion!r}; pass 'bce_dice' or a callable")
@@ -125,6 +137,8 @@ class GraphedEval:
                 with torch.no_grad():      # a RegionLoss / MulticlassLoss keeps its workspace (counts, class weights) per shape:
                     # allocated here, outside the capture
                     self._fused(warm, t)
+            if self._surface is not None:      # its workspace, out and stats of this shape: allocated outside the capture too
+                self._surface(warm, t)
             del warm
             # weight copies registered by that forward leave the pack cache without its pointer tables: build them now
             # (GraphedStep._setup does the same after its dry run), the captured refresh must find them in place
@@ -142,6 +156,7 @@ class GraphedEval:
             if self._fused_loss:
                 with torch.no_grad():      # no gradient: uz_bce_dice / uz_region_loss / uz_class_loss run with dlogits = NULL
                     g.loss, g.dice = self._fused(g.outputs, g.t)
+            g.surface = self._surface(g.outputs, g.t) if self._surface is not None else None
         _check_capture(g.graph, "evaluation graph")
         g.folded, g.unfolded = self._last_counts
         return g
@@ -171,6 +186,7 @@ class GraphedEval:
                 g.t.copy_(target)
         g.graph.replay()
         self.outputs = g.outputs
+        self.surface = g.surface
         self.folded_layers, self.unfolded_layers = g.folded, g.unfolded
         if self._fused_loss:
             self.loss, self.dice = g.loss, g.dice
@@ -183,20 +199,49 @@ class GraphedEval:
     # ------------------------------------------------------------------ one pass over a loader
     def evaluate(self, loader) -> Tuple[float, float]:
         """validate_one_epoch (training_loop.py:147-180): the means over the loader's batches of the per-batch loss and Dice.
-        Batches are (image, mask, ...) sequences; the sums stay on the device (float64) and are read back once."""
+        Batches are (image, mask, ...) sequences; the sums stay on the device (float64) and are read back once.
+        With ``surface`` the same read-back carries, per pair column, the sums of hd / hdq / assd over the pairs of state 0
+        (float64) and the counts of the four states (int64): ``surface_summary`` holds their means over the valid (image, pair)
+        occurrences of the pass (nan for a column with none) and the counts."""
         dev = self._check_model()
         tot = torch.zeros(2, dtype=torch.float64, device=dev)
+        ssum = scnt = None
         n = 0
         for batch in loader:
             loss, dice = self(batch[0], batch[1])
             tot += torch.stack((loss.detach().double().reshape(()), dice.detach().double().reshape(())))
+            if self.surface is not None:
+                out, stats = self.surface
+                state = stats[..., 5]                                     # (N, P)
+                if ssum is None:
+                    ssum = torch.zeros(3, out.shape[1], dtype=torch.float64, device=dev)
+                    scnt = torch.zeros(4, out.shape[1], dtype=torch.int64, device=dev)
+                elif ssum.shape[1] != out.shape[1]:
+                    raise ValueError("GraphedEval.evaluate: the number of surface pairs per image changed during the pass")
+                # the values of a pair whose state is not 0 are 0: the plain sum over the images is the sum over the valid ones
+                ssum += out[..., :3].double().sum(0).t()
+                scnt += torch.stack([(state == s).sum(0) for s in range(4)])
             n += 1
         if n == 0:
             raise ValueError("GraphedEval.evaluate: the loader yielded no batch")
-        mean = (tot / n).tolist()
+        if ssum is None:
+            mean = (tot / n).tolist()
+            return mean[0], mean[1]
+        P = ssum.shape[1]
+        # ONE read-back: the float64 means and sums travel as their bit patterns in front of the int64 counts
+        host = torch.cat(((tot / n).view(torch.int64), ssum.reshape(-1).view(torch.int64), scnt.reshape(-1))).cpu()
+        mean = host[:2].view(torch.float64).tolist()
+        sums = host[2:2 + 3 * P].view(torch.float64).reshape(3, P)
+        cnts = host[2 + 3 * P:].reshape(4, P)
+        valid = cnts[0].double()
+        means = torch.where(valid > 0, sums / valid.clamp(min=1.0), torch.full_like(sums, float("nan")))
+        self.surface_summary = {"hd": means[0].tolist(), "hdq": means[1].tolist(), "assd": means[2].tolist(),
+                                "n_valid": cnts[0].tolist(), "n_pred_empty": cnts[1].tolist(), "n_target_empty": cnts[2].tolist(),
+                                "n_both_empty": cnts[3].tolist(), "percentile": self._surface.percentile}
         return mean[0], mean[1]
 
     def describe(self) -> str:
         crit = "" if self._fused_loss else " + eager criterion"
         fold = ", eval BatchNorm folded into the convolution epilogues" if self.fold_bn else ""
-        return f"hipGraph(fwd{'+loss+dice' if self._fused_loss else ''}) per input shape{crit}{fold}"
+        surf = "+surface" if self._surface is not None else ""
+        return f"hipGraph(fwd{'+loss+dice' if self._fused_loss else ''}{surf}) per input shape{crit}{fold}"

@@ -1669,3 +1669,28 @@ def augment_apply(desc: "L.AugmentDesc", image: torch.Tensor, mask: Optional[tor
     with _Timed("augment_apply", 0.0, nb):
         L.check(L.load().uz_augment_apply(byref(desc), image.data_ptr(), _p(mask), params.data_ptr(), _p(disp),
                                           image_out.data_ptr(), _p(mask_out), L.stream_ptr()), "uz_augment_apply")
+
+
+# ---- SurfaceMetrics: Hausdorff / HD95 / ASSD of the thresholded maps (uz_surface.hip) ----------------------------------------
+def surface_grid(desc: "L.SurfaceDesc") -> tuple:
+    """(workgroups, units) of the column pass of uz_surface_metrics for this descriptor: units > workgroups means workgroups
+    walk"""
+    return L.surface_grid(desc)
+
+
+def surface_metrics(desc: "L.SurfaceDesc", logits: torch.Tensor, target: torch.Tensor, out: torch.Tensor, stats: torch.Tensor,
+                    workspace: torch.Tensor) -> None:
+    """out (N, P, 4) fp32 = hd, hdq, assd, 0 and stats (N, P, 8) int64 <- logits (N, C, H, W) fp32 against target: fp32
+    (N, C, H, W) maps (UZ_SURFACE_BINARY) or int32 (N, H, W) labels (UZ_SURFACE_CLASS); seven launches"""
+    L.require_cuda(logits, target, out, stats, workspace)
+    for t in (logits, target, out, stats, workspace):
+        assert t.is_contiguous()
+    cls = desc.mode == L.SURFACE_CLASS
+    P = desc.C - desc.first_class if cls else desc.C
+    assert logits.dtype == out.dtype == torch.float32 and stats.dtype == torch.int64
+    assert target.dtype == (torch.int32 if cls else torch.float32)
+    assert tuple(logits.shape) == (desc.N, desc.C, desc.H, desc.W)
+    assert tuple(target.shape) == ((desc.N, desc.H, desc.W) if cls else tuple(logits.shape))
+    assert tuple(out.shape) == (desc.N, P, 4) and tuple(stats.shape) == (desc.N, P, 8)
+    with _Timed("surface_metrics", 0.0, 4.0 * (logits.numel() + target.numel())):
+        L.surface_metrics(desc, logits, target, out, stats, workspace)
