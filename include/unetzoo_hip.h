@@ -1108,6 +1108,78 @@ int uz_surface_grid(const uz_surface_desc* d, int* units /* nullable */);
 int uz_surface_metrics(const uz_surface_desc* d, const float* logits, const void* target, float* out, long long* stats,
                        void* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mask post-processing, per (image, plane), every result an integer that scipy.ndimage gives too.  uz_postproc.hip
+ * UZ_POST_BINARY: x (N, C, H, W) fp32; plane = x > thr, every channel a plane: P = C.  Logits with thr = 0 or
+ *   probabilities with thr = 0.5.
+ * UZ_POST_CLASS : x (N, C, H, W) fp32 with C = K classes; plane c = (argmax_K == c), ties to the lowest index, for
+ *   c = first_class .. K - 1: P = K - first_class.
+ * Per plane, in this order:
+ *   1. fill_holes: add every pixel of the complement that is not 4-connected, within the complement, to a pixel on the
+ *      picture's edge (scipy.ndimage.binary_fill_holes, default structure: the cross whatever `connectivity` is)
+ *   2. components with connectivity 1 (cross) or 2 (3 x 3 square); a component's root is its smallest index i W + j
+ *   3. drop the components with area < min_area
+ *   4. keep_largest = k > 0: keep the k components of largest area, ties to the smaller root
+ * mask   (N, P, H, W) u8   the surviving pixels, 0 / 1
+ * labels (N, P, H, W) i32  the survivors numbered 1 .. n in raster order of their roots = scipy.ndimage.label(mask)[0]
+ * class_map (N, H, W) u8   class mode: the argmax class where its plane kept the pixel, else the lowest class whose final
+ *                          plane holds it (a filled hole), else 0
+ * stats  (N, P, 8) i64     components after step 1, components kept, area after step 1, area kept, pixels added by step 1,
+ *                          the largest area among the components of at least min_area, error word, 0
+ * comps  (N, P, 8, 8) i64  the eight (keep_largest, if smaller) largest kept components in the order of step 4, each
+ *                          area, i_min, j_min, i_max, j_max, sum i, sum j, root; unused records are zero
+ * labels and class_map may be null.  The error word is non-zero when a bounded find / union loop ran out (H W steps, a true
+ * bound: a bug, never a property of the input); the results of that plane are then undefined.
+ * The launches of a call depend on the descriptor alone: 18 (+ 4 with fill_holes, + 1 in the class mode); no allocation,
+ * no memset, no host synchronisation; the workspace (uz_postproc_workspace_bytes, 16-byte aligned) is cleared by the first
+ * launch.  No workgroup waits for another inside a launch.  uz_postproc_grid() returns the workgroups of the per-unit
+ * launches and (units, nullable) the units they share out (a unit: 256 consecutive pixels of a plane).
+ * UZ_EINVAL before any launch: null descriptor / pointer, unknown mode, N, C, H or W < 1, H or W > 4096, in the class mode
+ * K outside [2, UZ_CLASS_MAX_K] or first_class outside [0, K), connectivity not 1 or 2, fill_holes not 0 or 1, min_area < 0,
+ * keep_largest outside [0, UZ_POST_MAX_KEEP], thr NaN, N C H W >= 2^31, class_map in the binary mode, tensors misaligned
+ * (x, labels 4 bytes; stats, comps 8; workspace 16) or overlapping. */
+#define UZ_POST_BINARY 0
+#define UZ_POST_CLASS 1
+#define UZ_POST_MAX_KEEP 8
+typedef struct uz_postproc_desc {
+  int mode;         /* UZ_POST_* */
+  int N, C, H, W;   /* C: channels (binary) or classes K (class mode) */
+  int first_class;  /* class mode: the first class that is a plane (1 leaves the background out) */
+  int connectivity; /* 1 | 2 */
+  int fill_holes;   /* 0 | 1 */
+  int min_area;     /* >= 0 */
+  int keep_largest; /* 0 .. UZ_POST_MAX_KEEP; 0 = all */
+  float thr;        /* binary mode */
+  int reserved;
+} uz_postproc_desc;
+long long uz_postproc_workspace_bytes(const uz_postproc_desc* d); /* < 0: refused */
+int uz_postproc_grid(const uz_postproc_desc* d, int* units /* nullable */);
+int uz_postproc(const uz_postproc_desc* d, const float* x, unsigned char* mask, int* labels /* nullable */,
+                unsigned char* class_map /* nullable */, long long* stats, long long* comps, void* workspace, void* stream);
+
+/* Flip test-time augmentation.  uz_tta.hip.  views: a non-empty bit set of 1 identity, 2 hflip (along W), 4 vflip (along H),
+ * 8 hvflip; V = its bit count, the view order is the bit order.
+ * uz_flip_views: out[v] (N, C, H, W) fp32 = view v of x; `out` is a HOST array of V device pointers.  One launch.
+ * uz_tta_merge : prob (N, C, H, W) fp32 = mean over the views of sigmoid (UZ_POST_BINARY) or softmax over the C = K classes
+ *   (UZ_POST_CLASS) of logits[v] (N, C, H, W, `dtype` UZ_F32 or UZ_BF16; a HOST array of V device pointers), each read through
+ *   its inverse flip.  fp32 arithmetic, the views added in view order, then divided by V: no atomics, bit-reproducible.  One
+ *   launch.  With views = 1 it is the plain sigmoid / softmax.
+ * uz_mask_decide: the decision without any component step: mask (N, P, H, W) u8 = x > thr per channel (binary) or the
+ *   one-hot planes of argmax_K for the classes from first_class on (class mode, ties to the lowest index), class_map
+ *   (N, H, W) u8 = argmax_K (class mode, nullable).  `views` and `dtype` of the descriptor must be valid and are not used. */
+typedef struct uz_tta_desc {
+  int mode;         /* UZ_POST_* */
+  int N, C, H, W;
+  int views;        /* bit set, 1 .. 15 */
+  int dtype;        /* of the logits of uz_tta_merge */
+  int reserved;
+} uz_tta_desc;
+int uz_tta_num_views(int views); /* V, or < 0 */
+int uz_flip_views(const uz_tta_desc* d, const float* x, float* const* out, void* stream);
+int uz_tta_merge(const uz_tta_desc* d, const void* const* logits, float* prob, void* stream);
+int uz_mask_decide(const uz_tta_desc* d, const float* x, float thr, int first_class, unsigned char* mask,
+                   unsigned char* class_map /* nullable */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

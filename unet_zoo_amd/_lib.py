@@ -58,6 +58,8 @@ EXPORTS = (
     "uz_class_loss_workspace_bytes", "uz_class_loss",
     "uz_augment_params", "uz_augment_grid", "uz_augment_apply",
     "uz_surface_workspace_bytes", "uz_surface_grid", "uz_surface_metrics",
+    "uz_postproc_workspace_bytes", "uz_postproc_grid", "uz_postproc",
+    "uz_tta_num_views", "uz_flip_views", "uz_tta_merge", "uz_mask_decide",
 )
 
 
@@ -197,6 +199,23 @@ class SurfaceDesc(Structure):
     """uz_surface_desc"""
     _fields_ = [(n, c_int) for n in ("mode", "N", "C", "H", "W", "first_class", "ignore_index", "reserved")] \
         + [("q", c_double), ("spacing", c_double)]
+
+
+POST_BINARY, POST_CLASS = 0, 1
+POST_MAX_KEEP = 8
+POST_MAX_HW = 4096
+TTA_VIEWS = {"identity": 1, "hflip": 2, "vflip": 4, "hvflip": 8}      # bit of a view; the view order is the bit order
+
+
+class PostprocDesc(Structure):
+    """uz_postproc_desc"""
+    _fields_ = [(n, c_int) for n in ("mode", "N", "C", "H", "W", "first_class", "connectivity", "fill_holes", "min_area",
+                                     "keep_largest")] + [("thr", c_float), ("reserved", c_int)]
+
+
+class TtaDesc(Structure):
+    """uz_tta_desc"""
+    _fields_ = [(n, c_int) for n in ("mode", "N", "C", "H", "W", "views", "dtype", "reserved")]
 
 
 class HipLibraryError(RuntimeError):
@@ -387,6 +406,13 @@ def load():
     lib.uz_surface_workspace_bytes.argtypes = [POINTER(SurfaceDesc)]
     lib.uz_surface_grid.argtypes = [POINTER(SurfaceDesc), POINTER(c_int)]
     lib.uz_surface_metrics.argtypes = [POINTER(SurfaceDesc), vp, vp, vp, vp, vp, vp]
+    lib.uz_postproc_workspace_bytes.argtypes = [POINTER(PostprocDesc)]
+    lib.uz_postproc_grid.argtypes = [POINTER(PostprocDesc), POINTER(c_int)]
+    lib.uz_postproc.argtypes = [POINTER(PostprocDesc), vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.uz_tta_num_views.argtypes = [c_int]
+    lib.uz_flip_views.argtypes = [POINTER(TtaDesc), vp, POINTER(c_void_p), vp]
+    lib.uz_tta_merge.argtypes = [POINTER(TtaDesc), POINTER(c_void_p), vp, vp]
+    lib.uz_mask_decide.argtypes = [POINTER(TtaDesc), vp, c_float, c_int, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("uz_last_error_string", "uz_source_hash"):
@@ -460,6 +486,49 @@ def surface_metrics(desc: "SurfaceDesc", logits: torch.Tensor, target: torch.Ten
     """uz_surface_metrics() on the current stream: seven launches, no allocation, no host read"""
     check(load().uz_surface_metrics(ctypes.byref(desc), logits.data_ptr(), target.data_ptr(), out.data_ptr(), stats.data_ptr(),
                                     workspace.data_ptr(), stream_ptr()), "uz_surface_metrics")
+
+
+def postproc_workspace_bytes(desc: "PostprocDesc") -> int:
+    """uz_postproc_workspace_bytes(): bytes of workspace a uz_postproc call with this descriptor needs"""
+    return check_count(load().uz_postproc_workspace_bytes(ctypes.byref(desc)), "uz_postproc_workspace_bytes")
+
+
+def postproc_grid(desc: "PostprocDesc") -> tuple:
+    """uz_postproc_grid(): (workgroups, units) of the per-unit launches of uz_postproc for this descriptor"""
+    units = c_int(0)
+    grid = check_count(load().uz_postproc_grid(ctypes.byref(desc), ctypes.byref(units)), "uz_postproc_grid")
+    return grid, units.value
+
+
+def _ptr(t) -> "int | None":
+    return t.data_ptr() if t is not None else None
+
+
+def postproc(desc: "PostprocDesc", x: torch.Tensor, mask: torch.Tensor, labels, class_map, stats: torch.Tensor, comps: torch.Tensor,
+             workspace: torch.Tensor) -> None:
+    """uz_postproc() on the current stream: a fixed number of launches, no allocation, no host read"""
+    check(load().uz_postproc(ctypes.byref(desc), x.data_ptr(), mask.data_ptr(), _ptr(labels), _ptr(class_map), stats.data_ptr(),
+                             comps.data_ptr(), workspace.data_ptr(), stream_ptr()), "uz_postproc")
+
+
+def _ptr_table(tensors):
+    return (c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def flip_views(desc: "TtaDesc", x: torch.Tensor, views) -> None:
+    """uz_flip_views() on the current stream: one launch (`views`: the V output tensors; a HOST pointer table)"""
+    check(load().uz_flip_views(ctypes.byref(desc), x.data_ptr(), _ptr_table(views), stream_ptr()), "uz_flip_views")
+
+
+def tta_merge(desc: "TtaDesc", logits, prob: torch.Tensor) -> None:
+    """uz_tta_merge() on the current stream: one launch (`logits`: the V tensors in view order)"""
+    check(load().uz_tta_merge(ctypes.byref(desc), _ptr_table(logits), prob.data_ptr(), stream_ptr()), "uz_tta_merge")
+
+
+def mask_decide(desc: "TtaDesc", x: torch.Tensor, thr: float, first_class: int, mask: torch.Tensor, class_map) -> None:
+    """uz_mask_decide() on the current stream: one launch"""
+    check(load().uz_mask_decide(ctypes.byref(desc), x.data_ptr(), float(thr), int(first_class), mask.data_ptr(), _ptr(class_map),
+                                stream_ptr()), "uz_mask_decide")
 
 
 def set_cu_reserve(n: int) -> None:

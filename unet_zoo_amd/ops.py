@@ -1694,3 +1694,79 @@ def surface_metrics(desc: "L.SurfaceDesc", logits: torch.Tensor, target: torch.T
     assert tuple(out.shape) == (desc.N, P, 4) and tuple(stats.shape) == (desc.N, P, 8)
     with _Timed("surface_metrics", 0.0, 4.0 * (logits.numel() + target.numel())):
         L.surface_metrics(desc, logits, target, out, stats, workspace)
+
+
+# ---- MaskPostprocess / GraphedPredict: components, hole filling, flip TTA (uz_postproc.hip, uz_tta.hip) -----------------------
+def postproc_grid(desc: "L.PostprocDesc") -> tuple:
+    """(workgroups, units) of the per-unit launches of uz_postproc for this descriptor: units > workgroups means workgroups
+    walk"""
+    return L.postproc_grid(desc)
+
+
+def postproc(desc: "L.PostprocDesc", x: torch.Tensor, mask: torch.Tensor, labels: Optional[torch.Tensor],
+             class_map: Optional[torch.Tensor], stats: torch.Tensor, comps: torch.Tensor, workspace: torch.Tensor) -> None:
+    """mask (N, P, H, W) u8, labels (N, P, H, W) i32 or None, class_map (N, H, W) u8 or None, stats (N, P, 8) i64 and comps
+    (N, P, 8, 8) i64 <- x (N, C, H, W) fp32 logits or probabilities (include/unetzoo_hip.h); launches fixed by the descriptor"""
+    L.require_cuda(x, mask, labels, class_map, stats, comps, workspace)
+    for t in (x, mask, labels, class_map, stats, comps, workspace):
+        assert t is None or t.is_contiguous()
+    cls = desc.mode == L.POST_CLASS
+    P = desc.C - desc.first_class if cls else desc.C
+    shape = (desc.N, P, desc.H, desc.W)
+    assert x.dtype == torch.float32 and tuple(x.shape) == (desc.N, desc.C, desc.H, desc.W)
+    assert mask.dtype == torch.uint8 and tuple(mask.shape) == shape
+    assert labels is None or (labels.dtype == torch.int32 and tuple(labels.shape) == shape)
+    assert class_map is None or (cls and class_map.dtype == torch.uint8 and tuple(class_map.shape) == (desc.N, desc.H, desc.W))
+    assert stats.dtype == comps.dtype == torch.int64 and tuple(stats.shape) == (desc.N, P, 8) and tuple(comps.shape) == (desc.N, P, 8, 8)
+    with _Timed("postproc", 0.0, 4.0 * x.numel()):
+        L.postproc(desc, x, mask, labels, class_map, stats, comps, workspace)
+
+
+def tta_views(tta) -> int:
+    """the bit set of the views of a `tta` tuple of flip names; the identity is always a view"""
+    bits = L.TTA_VIEWS["identity"]
+    for name in tta:
+        if name not in L.TTA_VIEWS:
+            raise ValueError(f"tta: unknown view {name!r}; the views are {sorted(L.TTA_VIEWS)}")
+        bits |= L.TTA_VIEWS[name]
+    return bits
+
+
+def _tta_desc(mode: int, shape, views: int, dtype: torch.dtype) -> "L.TtaDesc":
+    N, C, H, W = (int(s) for s in shape)
+    return L.TtaDesc(mode, N, C, H, W, views, L.dtype_code(dtype), 0)
+
+
+def flip_views(x: torch.Tensor, views: int, out) -> None:
+    """out[v] <- view v of x (N, C, H, W) fp32, for the views of the bit set in bit order; one launch"""
+    L.require_cuda(x, *out)
+    assert x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
+    assert len(out) == bin(views).count("1")
+    for o in out:
+        assert o.dtype == torch.float32 and o.shape == x.shape and o.is_contiguous()
+    with _Timed("flip_views", 0.0, 4.0 * x.numel() * (1 + len(out))):
+        L.flip_views(_tta_desc(L.POST_BINARY, x.shape, views, torch.float32), x, out)
+
+
+def tta_merge(logits, views: int, mode: int, prob: torch.Tensor) -> None:
+    """prob (N, C, H, W) fp32 <- the mean over the views of sigmoid (L.POST_BINARY) or softmax over C (L.POST_CLASS) of
+    logits[v] (fp32 or bf16, all alike), each read through its inverse flip; one launch, bit-reproducible"""
+    L.require_cuda(prob, *logits)
+    assert len(logits) == bin(views).count("1") and len(logits) >= 1
+    for t in logits:
+        assert t.dtype == logits[0].dtype and t.shape == prob.shape and t.is_contiguous()
+    assert prob.dtype == torch.float32 and prob.dim() == 4 and prob.is_contiguous()
+    with _Timed("tta_merge", 0.0, 4.0 * prob.numel() * (1 + len(logits))):
+        L.tta_merge(_tta_desc(mode, prob.shape, views, logits[0].dtype), logits, prob)
+
+
+def mask_decide(x: torch.Tensor, mode: int, thr: float, first_class: int, mask: torch.Tensor, class_map: Optional[torch.Tensor]) -> None:
+    """mask (N, P, H, W) u8 [, class_map (N, H, W) u8] <- x > thr per channel, or the one-hot planes of argmax_K; one launch"""
+    L.require_cuda(x, mask, class_map)
+    N, C, H, W = x.shape
+    P = C - first_class if mode == L.POST_CLASS else C
+    assert x.dtype == torch.float32 and x.is_contiguous() and mask.is_contiguous() and mask.dtype == torch.uint8
+    assert tuple(mask.shape) == (N, P, H, W)
+    assert class_map is None or (class_map.dtype == torch.uint8 and tuple(class_map.shape) == (N, H, W) and class_map.is_contiguous())
+    with _Timed("mask_decide", 0.0, 4.0 * x.numel()):
+        L.mask_decide(_tta_desc(mode, x.shape, 1, torch.float32), x, thr, first_class, mask, class_map)
