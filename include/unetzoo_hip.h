@@ -1180,6 +1180,49 @@ int uz_tta_merge(const uz_tta_desc* d, const void* const* logits, float* prob, v
 int uz_mask_decide(const uz_tta_desc* d, const float* x, float thr, int first_class, unsigned char* mask,
                    unsigned char* class_map /* nullable */, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Sliding-window inference: cutting overlapping windows and blending their probabilities.  uz_tile.hip
+ * Along one axis an image of `size` pixels lies on a canvas of D = max(size, window) pixels, at offset
+ * floor((window - size) / 2) when it is smaller than the window (else 0).  uz_tile_plan() writes the tile starts on that
+ * canvas by the rule of MONAI's sliding_window_inference: step s = max(int(window (1 - overlap)), 1), n = 1 if D == window
+ * else ceil((D - window) / s) + 1 tiles, start_i = min(i s, D - window): the last tile is shifted back, none sticks out.
+ * It returns n, or -1: size or window < 1, overlap outside [0, 0.75] or NaN, starts null, n > cap or n > UZ_TILE_MAX_AXIS.
+ * Pure host code.
+ * Tile t of the list is (n ny + iy) nx + ix; ys[ny] / xs[nx] are HOST tables of starts (copied into the kernel arguments),
+ * strictly ascending from 0 to D - window with no gap wider than the window.
+ * uz_tile_gather: out (tn, C, th, tw) fp32 = the tiles [t0, t0 + tn) of x (N, C, H, W) fp32, an exact copy; canvas pixels
+ *   outside the image are 0 (UZ_TILE_PAD_ZERO) or the image mirrored without repeating its edge (UZ_TILE_PAD_REFLECT, the
+ *   indexing of torch.nn.functional.pad(mode="reflect"); needs pad < size).  One launch.
+ * uz_tile_blend : out (N, C, H, W) fp32 = sum_k w_k p_k / sum_k w_k over the tiles of `tiles` (N ny nx, C, th, tw) fp32
+ *   that cover the pixel, in tile order (iy ascending, then ix ascending), w = fmaxf(gh[y'] gw[x'], 1e-3f) at the pixel's
+ *   place (y', x') in that tile; gh[th], gw[tw] fp32 DEVICE tables.  One thread owns a pixel: no atomics, fp32 products, sums
+ *   and one IEEE division, bit-reproducible.  Only the H x W image region of the canvas is written.  One launch.
+ * UZ_EINVAL before any launch: null descriptor / pointer, N, C, H, W, th or tw < 1, ny or nx outside [1, UZ_TILE_MAX_AXIS],
+ * a start table that breaks the rule above, more than UZ_TILE_MAX_COVER tiles over one pixel along an axis, unknown pad_mode,
+ * reflect with pad >= size, [t0, t0 + tn) outside the list, N C H W, T C th tw or tn C th tw >= 2^31, tensors misaligned
+ * (4 bytes) or output overlapping an input. */
+#define UZ_TILE_MAX_AXIS 256
+#define UZ_TILE_MAX_COVER 8
+#define UZ_TILE_PAD_ZERO 0
+#define UZ_TILE_PAD_REFLECT 1
+typedef struct uz_tile_gather_desc {
+  int N, C, H, W;   /* the image batch */
+  int th, tw;       /* the window */
+  int ny, nx;       /* tiles along H / W */
+  int pad_mode;     /* UZ_TILE_PAD_* */
+  int t0, tn;       /* the tiles [t0, t0 + tn) of the list of N ny nx */
+  int reserved;
+} uz_tile_gather_desc;
+typedef struct uz_tile_blend_desc {
+  int N, C, H, W;   /* the blended output */
+  int th, tw;       /* the window */
+  int ny, nx;       /* tiles along H / W */
+} uz_tile_blend_desc;
+int uz_tile_plan(int size, int window, double overlap, int* starts, int cap); /* n, or -1 */
+int uz_tile_gather(const uz_tile_gather_desc* d, const int* ys, const int* xs, const float* x, float* out, void* stream);
+int uz_tile_blend(const uz_tile_blend_desc* d, const int* ys, const int* xs, const float* tiles, const float* gh,
+                  const float* gw, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,10 +13,11 @@ from .augment import GpuAugment
 from .surface import SurfaceMetrics
 from .postprocess import MaskPostprocess
 from .predict import GraphedPredict
+from .tiled import SlidingWindowPredict
 from .config import Config, load_config
 
 __version__ = "0.1.0"
 __all__ = ["create_model", "list_models", "get_model_config", "hip_models", "set_default_dtype",
            "get_default_dtype", "GraphedStep", "GraphedEval", "RegionLoss", "MulticlassLoss", "GpuAugment", "SurfaceMetrics",
-           "MaskPostprocess", "GraphedPredict",
+           "MaskPostprocess", "GraphedPredict", "SlidingWindowPredict",
            "Config", "load_config"]

@@ -60,6 +60,7 @@ EXPORTS = (
     "uz_surface_workspace_bytes", "uz_surface_grid", "uz_surface_metrics",
     "uz_postproc_workspace_bytes", "uz_postproc_grid", "uz_postproc",
     "uz_tta_num_views", "uz_flip_views", "uz_tta_merge", "uz_mask_decide",
+    "uz_tile_plan", "uz_tile_gather", "uz_tile_blend",
 )
 
 
@@ -216,6 +217,20 @@ class PostprocDesc(Structure):
 class TtaDesc(Structure):
     """uz_tta_desc"""
     _fields_ = [(n, c_int) for n in ("mode", "N", "C", "H", "W", "views", "dtype", "reserved")]
+
+
+TILE_MAX_AXIS, TILE_MAX_COVER = 256, 8
+TILE_PADS = {"constant": 0, "reflect": 1}       # UZ_TILE_PAD_ZERO, UZ_TILE_PAD_REFLECT
+
+
+class TileGatherDesc(Structure):
+    """uz_tile_gather_desc"""
+    _fields_ = [(n, c_int) for n in ("N", "C", "H", "W", "th", "tw", "ny", "nx", "pad_mode", "t0", "tn", "reserved")]
+
+
+class TileBlendDesc(Structure):
+    """uz_tile_blend_desc"""
+    _fields_ = [(n, c_int) for n in ("N", "C", "H", "W", "th", "tw", "ny", "nx")]
 
 
 class HipLibraryError(RuntimeError):
@@ -413,6 +428,9 @@ def load():
     lib.uz_flip_views.argtypes = [POINTER(TtaDesc), vp, POINTER(c_void_p), vp]
     lib.uz_tta_merge.argtypes = [POINTER(TtaDesc), POINTER(c_void_p), vp, vp]
     lib.uz_mask_decide.argtypes = [POINTER(TtaDesc), vp, c_float, c_int, vp, vp, vp]
+    lib.uz_tile_plan.argtypes = [c_int, c_int, c_double, POINTER(c_int), c_int]
+    lib.uz_tile_gather.argtypes = [POINTER(TileGatherDesc), POINTER(c_int), POINTER(c_int), vp, vp, vp]
+    lib.uz_tile_blend.argtypes = [POINTER(TileBlendDesc), POINTER(c_int), POINTER(c_int), vp, vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("uz_last_error_string", "uz_source_hash"):
@@ -529,6 +547,29 @@ def mask_decide(desc: "TtaDesc", x: torch.Tensor, thr: float, first_class: int, 
     """uz_mask_decide() on the current stream: one launch"""
     check(load().uz_mask_decide(ctypes.byref(desc), x.data_ptr(), float(thr), int(first_class), mask.data_ptr(), _ptr(class_map),
                                 stream_ptr()), "uz_mask_decide")
+
+
+def tile_plan(size: int, window: int, overlap: float) -> list:
+    """uz_tile_plan(): the tile starts along one axis (host code; no GPU call)"""
+    starts = (c_int * TILE_MAX_AXIS)()
+    n = check_count(load().uz_tile_plan(int(size), int(window), float(overlap), starts, TILE_MAX_AXIS), "uz_tile_plan")
+    return [int(starts[i]) for i in range(n)]
+
+
+def _int_table(values):
+    return (c_int * len(values))(*[int(v) for v in values])
+
+
+def tile_gather(desc: "TileGatherDesc", ys, xs, x: torch.Tensor, out: torch.Tensor) -> None:
+    """uz_tile_gather() on the current stream: one launch (`ys`, `xs`: HOST start tables, copied into the kernel arguments)"""
+    check(load().uz_tile_gather(ctypes.byref(desc), _int_table(ys), _int_table(xs), x.data_ptr(), out.data_ptr(), stream_ptr()),
+          "uz_tile_gather")
+
+
+def tile_blend(desc: "TileBlendDesc", ys, xs, tiles: torch.Tensor, gh: torch.Tensor, gw: torch.Tensor, out: torch.Tensor) -> None:
+    """uz_tile_blend() on the current stream: one launch (`gh`, `gw`: DEVICE weight tables)"""
+    check(load().uz_tile_blend(ctypes.byref(desc), _int_table(ys), _int_table(xs), tiles.data_ptr(), gh.data_ptr(), gw.data_ptr(),
+                               out.data_ptr(), stream_ptr()), "uz_tile_blend")
 
 
 def set_cu_reserve(n: int) -> None:

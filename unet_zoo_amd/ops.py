@@ -1770,3 +1770,53 @@ def mask_decide(x: torch.Tensor, mode: int, thr: float, first_class: int, mask: 
     assert class_map is None or (class_map.dtype == torch.uint8 and tuple(class_map.shape) == (N, H, W) and class_map.is_contiguous())
     with _Timed("mask_decide", 0.0, 4.0 * x.numel()):
         L.mask_decide(_tta_desc(mode, x.shape, 1, torch.float32), x, thr, first_class, mask, class_map)
+
+
+# ---- SlidingWindowPredict: cutting windows and blending their probabilities (uz_tile.hip) -------------------------------------
+def tile_plan(size: int, window: int, overlap: float) -> list:
+    """the tile starts along one axis of `size` pixels, on the canvas of max(size, window) pixels: uz_tile_plan itself, so the
+    plan and the kernels cannot disagree (MONAI's rule; the last tile is shifted back)"""
+    return L.tile_plan(size, window, overlap)
+
+
+def tile_weights(n: int, blend: str = "gaussian", sigma_scale: float = 0.125) -> torch.Tensor:
+    """the window weight along one axis of n pixels, fp32 on the host: ones ("constant") or
+    exp(-(i - (n - 1) / 2)^2 / (2 (sigma_scale n)^2)) ("gaussian"), computed in float64 and rounded once"""
+    if blend == "constant":
+        return torch.ones(int(n), dtype=torch.float32)
+    if blend != "gaussian":
+        raise ValueError(f"blend: unknown window weight {blend!r}; 'constant' or 'gaussian'")
+    if not float(sigma_scale) > 0.0:
+        raise ValueError(f"sigma_scale must be positive, got {sigma_scale!r}")
+    i = torch.arange(int(n), dtype=torch.float64)
+    return torch.exp(-(i - (n - 1) / 2.0) ** 2 / (2.0 * (float(sigma_scale) * n) ** 2)).float()
+
+
+def tile_gather(x: torch.Tensor, ys, xs, window, pad_mode: str, t0: int, out: torch.Tensor) -> None:
+    """out (tn, C, th, tw) fp32 <- the tiles [t0, t0 + tn) of x (N, C, H, W) fp32; tile t is (n ny + iy) nx + ix with the starts
+    ys / xs of ops.tile_plan; an image smaller than the window is centred on it, the rest "constant" (zero) or "reflect"; one
+    launch, an exact copy"""
+    L.require_cuda(x, out)
+    if pad_mode not in L.TILE_PADS:
+        raise ValueError(f"pad_mode: unknown padding {pad_mode!r}; the paddings are {sorted(L.TILE_PADS)}")
+    th, tw = (int(v) for v in window)
+    assert x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
+    N, C, H, W = x.shape
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4 and tuple(out.shape[1:]) == (C, th, tw)
+    desc = L.TileGatherDesc(N, C, H, W, th, tw, len(ys), len(xs), L.TILE_PADS[pad_mode], int(t0), int(out.shape[0]), 0)
+    with _Timed("tile_gather", 0.0, 8.0 * out.numel()):
+        L.tile_gather(desc, ys, xs, x, out)
+
+
+def tile_blend(tiles: torch.Tensor, ys, xs, gh: torch.Tensor, gw: torch.Tensor, out: torch.Tensor) -> None:
+    """out (N, C, H, W) fp32 <- sum w p / sum w over the tiles (N ny nx, C, th, tw) fp32 that cover each pixel, in tile order,
+    w = max(gh[y'] gw[x'], 1e-3); the padding of the canvas is cropped; one launch, bit-reproducible"""
+    L.require_cuda(tiles, gh, gw, out)
+    assert tiles.dtype == out.dtype == gh.dtype == gw.dtype == torch.float32
+    assert tiles.dim() == 4 and out.dim() == 4 and tiles.is_contiguous() and out.is_contiguous() and gh.is_contiguous() and gw.is_contiguous()
+    N, C, H, W = out.shape
+    T, Ct, th, tw = tiles.shape
+    assert Ct == C and T == N * len(ys) * len(xs) and tuple(gh.shape) == (th,) and tuple(gw.shape) == (tw,)
+    desc = L.TileBlendDesc(N, C, H, W, th, tw, len(ys), len(xs))
+    with _Timed("tile_blend", 0.0, 4.0 * (tiles.numel() + out.numel())):
+        L.tile_blend(desc, ys, xs, tiles, gh, gw, out)
