@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 
 import unet_zoo_amd
 from oracle import torch_ref
+from storage_move import move_two_weights, twin_of  # tests/storage_move.py
 from unet_zoo_amd.engine import Engine
 from unet_zoo_amd.loss import loss_and_dice
 
@@ -216,6 +217,31 @@ def test_an_optimizer_step_between_two_calls_is_seen():
     assert next(iter(ev._graphs.values())) is g
     assert not _same(outs2, outs)
     assert _same(_flat(ev.outputs), outs2) and torch.equal(l2, loss2)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_a_parameter_on_new_storage_is_read_there(dtype):
+    """storage that moves without GraphedStep: the new capture must read the new addresses (tests/storage_move.py)"""
+    m, _ = _make("unet", dtype)
+    x, t = _batch()
+    with torch.no_grad():                     # the logits straddle zero, so that the Dice (a count of their signs) can move
+        head_bias = [p for n, p in m.named_parameters() if n.endswith("bias") and p.numel() == 1][-1]
+        head_bias -= _main(m(x)).float().median()
+    ev = unet_zoo_amd.GraphedEval(m, "bce_dice")
+    l0, d0 = ev(x, t)
+    torch.cuda.synchronize()
+    out0, l0, d0 = _main(ev.outputs).clone(), l0.clone(), d0.clone()
+    kept = move_two_weights(m)
+    outs, loss, dice = _eager(twin_of(m, lambda: _make("unet", dtype)[0]), x, t)
+    l1, d1 = ev(x, t)
+    torch.cuda.synchronize()
+    print(f"loss {l0.item():.6f} -> {l1.item():.6f} (eager {loss.item():.6f}), dice {d0.item():.6f} -> {d1.item():.6f} (eager {dice.item():.6f})")
+    assert _same(_flat(ev.outputs), outs) and torch.equal(l1, loss) and torch.equal(d1, dice)
+    assert not torch.equal(_main(ev.outputs), out0) and not torch.equal(l1, l0) and not torch.equal(d1, d0)
+    assert len(ev._graphs) == 1 and len(kept) == 2
+    # ... and so does the moved model's own eager forward from now on
+    outs2, loss2, dice2 = _eager(m, x, t)
+    assert _same(outs2, outs) and torch.equal(loss2, loss) and torch.equal(dice2, dice)
 
 
 def test_vnet_keeps_its_reference_semantics():

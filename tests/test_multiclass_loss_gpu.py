@@ -13,7 +13,7 @@ from unet_zoo_amd import MulticlassLoss, RegionLoss
 from unet_zoo_amd import _lib as L
 from unet_zoo_amd.graph import PhasedStep
 from unet_zoo_amd.optim import FlatClipAdamW
-from unet_zoo_amd.step import _check_capture
+from unet_zoo_amd.capture import _check_capture
 
 pytestmark = pytest.mark.gpu
 

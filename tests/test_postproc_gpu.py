@@ -14,6 +14,7 @@ import torch
 import postproc_ref as R  # tests/postproc_ref.py (pytest puts this directory on sys.path)
 import unet_zoo_amd
 from oracle import torch_ref
+from storage_move import move_two_weights, twin_of  # tests/storage_move.py
 from unet_zoo_amd import _lib, ops
 from unet_zoo_amd.postprocess import MaskPostprocess
 from unet_zoo_amd.predict import GraphedPredict
@@ -375,6 +376,27 @@ def test_an_optimizer_step_between_two_calls_is_seen():
     torch.cuda.synchronize()
     assert not torch.equal(pred.prob, prob0)
     assert torch.equal(pred.prob, want[0]) and torch.equal(mask, want[1]) and torch.equal(pred.labels, want[2])
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_a_parameter_on_new_storage_is_read_there(dtype):
+    """storage that moves without GraphedStep: the new capture must read the new addresses (tests/storage_move.py)"""
+    x = _x()
+    m = _centre(_make("unet", dtype), x)
+    pred = GraphedPredict(m, tta=("hflip",), postprocess=MaskPostprocess(min_area=2))
+    pred(x)
+    torch.cuda.synchronize()
+    prob0 = pred.prob.clone()
+    kept = move_two_weights(m)
+    want = _by_hand(twin_of(m, lambda: _make("unet", dtype)), x, 3, MaskPostprocess(min_area=2), _lib.POST_BINARY)
+    mask = pred(x)
+    torch.cuda.synchronize()
+    assert pred.captures == 2 and len(kept) == 2
+    assert torch.equal(pred.prob, want[0]) and torch.equal(mask, want[1]) and torch.equal(pred.labels, want[2])
+    assert not torch.equal(pred.prob, prob0)
+    # ... and so does the moved model's own eager forward from now on
+    again = _by_hand(m, x, 3, MaskPostprocess(min_area=2), _lib.POST_BINARY)
+    assert all(torch.equal(a, w) for a, w in zip(again[:3], want[:3]))
 
 
 @pytest.mark.parametrize("name,kw", [("u2net", {}), ("nested_unet", {"deep_supervision": True})])

@@ -13,7 +13,7 @@ from unet_zoo_amd import RegionLoss
 from unet_zoo_amd import _lib as L
 from unet_zoo_amd.loss import bce_dice_with_logits
 from unet_zoo_amd.optim import FlatClipAdamW
-from unet_zoo_amd.step import _check_capture
+from unet_zoo_amd.capture import _check_capture
 
 pytestmark = pytest.mark.gpu
 

@@ -153,10 +153,10 @@ def test_loss_in_the_graph_is_the_loss_of_the_replayed_logits():
 
 
 def test_capture_check_sees_memset_nodes():
-    """step._memset_nodes(): the guard GraphedStep applies to every graph it captures must really list the nodes -- a
+    """capture._memset_nodes(): the guard GraphedStep applies to every graph it captures must really list the nodes -- a
     multi-block torch reduction resets its semaphores with hipMemsetAsync (the node that acts only in the first replay
     on this stack), an elementwise op does not"""
-    from unet_zoo_amd import step as S
+    from unet_zoo_amd import capture as S
     big = torch.randn(1 << 24, device="cuda")
     out = torch.zeros((), device="cuda")
     side = torch.cuda.Stream()

@@ -14,6 +14,7 @@ import torch
 import tile_ref as T  # tests/tile_ref.py (pytest puts this directory on sys.path)
 import unet_zoo_amd
 from oracle import torch_ref
+from storage_move import move_two_weights, twin_of  # tests/storage_move.py
 from unet_zoo_amd import _lib, ops
 from unet_zoo_amd.postprocess import MaskPostprocess
 from unet_zoo_amd.predict import GraphedPredict
@@ -269,12 +270,14 @@ def test_unet_replay_equals_the_composition_by_hand(dtype):
     torch.cuda.synchronize()
     assert pred.captures == 2 and not torch.equal(want3[0], want[0])
     _same(pred, mask, want3)
-    # a parameter moved to new storage: one new capture
-    p.data = p.data.clone()
+    # two parameters moved to new storage, with new values: one new capture, which reads them there (tests/storage_move.py)
+    kept = move_two_weights(m)
+    before, want3 = want3, _by_hand(twin_of(m, lambda: _make("unet", dtype)), x, *args, MaskPostprocess(**kw), _lib.POST_BINARY)
     mask = pred(x)
     torch.cuda.synchronize()
-    assert pred.captures == 3
+    assert pred.captures == 3 and len(kept) == 2 and not torch.equal(want3[0], before[0])
     _same(pred, mask, want3)
+    _same(pred, mask, _by_hand(m, x, *args, MaskPostprocess(**kw), _lib.POST_BINARY))     # the moved model's own forwards, from now on
     masks = list(pred.predict([x, (x2, None)]))
     assert [tuple(k.shape) for k in masks] == [(2, 1, 72, 88), (1, 1, 24, 50)] and pred.captures == 4 and torch.equal(masks[0], want3[1])
 

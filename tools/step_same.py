@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Does a change of the Python engine leave every launch and every bit where it was?  For a refactor of engine.py / ops.py.
+"""Does a change of the Python engine leave every launch and every bit where it was?  For a refactor of engine.py / ops.py, or of
+the graphed runners on top of them.
 
     python tools/step_same.py record OUT.json [--only NAME,...]
     python tools/step_same.py compare A.json B.json [--log-only NAME,...]
@@ -90,6 +91,11 @@ def configs(nf):
     for dt in ("bf16", "fp32"):
         out.append((f"graphed_eval_fold_bn/unet/{dt}", dict(model="unet", kw={}, b=2, size=64, dtype=dt, mode="graphed_eval")))
         out.append((f"frozen_backward/unet/{dt}", dict(model="unet", kw={}, b=2, size=64, dtype=dt, mode="frozen")))
+        # the graphed runners through their public results (for a refactor of capture.py / step.py / evalstep.py / predict.py / tiled.py)
+        out.append((f"graphed_predict/unet/{dt}", dict(model="unet", kw={}, b=2, size=64, dtype=dt, mode="graphed_predict")))
+        out.append((f"tiled/unet/{dt}", dict(model="unet", kw={}, b=2, size=64, dtype=dt, mode="tiled")))
+        for crit in ("bce_dice", "callable"):
+            out.append((f"graphed_step/{crit}/unet/{dt}", dict(model="unet", kw={}, b=2, size=64, dtype=dt, mode="graphed_step", crit=crit)))
     for name in FOLDED:
         out.append((f"folds_on/{name}/bf16/N{nf}", dict(model=name, kw={}, b=nf, size=64, dtype="bf16", mode="train")))
     for s in OFF:
@@ -107,6 +113,64 @@ def _take_log():
     return log
 
 
+def _results(sha, tag, obj, names):
+    """the sha256 of every tensor in the public result fields `names` of a runner, under tag/"""
+    torch.cuda.synchronize()
+    for n in names:
+        v = getattr(obj, n)
+        for i, t in enumerate(_tensors(v) if v is not None else ()):
+            sha[f"{tag}/{n}{i}"] = _sha(t)
+        if v is None:
+            sha[f"{tag}/{n}"] = "none"
+
+
+def _centre(m, x):
+    """move the head's bias so that the logits of x straddle zero: a freshly initialised unet predicts one empty mask"""
+    with torch.no_grad():
+        bias = [p for n, p in m.named_parameters() if n.endswith("bias") and p.numel() == 1][-1]
+        bias -= m(x).float().median()
+
+
+def run_predict(cfg, m, x, sha):
+    """GraphedPredict / SlidingWindowPredict: the results of the capturing call, of a plain replay and of a replay after an in-place
+    parameter change; then the launches of one eager pass of the captured pipeline (a capture takes no timing events)"""
+    from unet_zoo_amd import MaskPostprocess
+    m.eval()
+    _centre(m, x)
+    if cfg["mode"] == "graphed_predict":
+        pred = unet_zoo_amd.GraphedPredict(m, tta=("hflip", "vflip"), postprocess=MaskPostprocess(fill_holes=True, min_area=4))
+        names = ("mask", "prob", "labels", "class_map", "stats", "comps", "outputs")
+    else:
+        x = torch.randn(2, 3, 72, 88, generator=torch.Generator().manual_seed(1)).cuda()
+        pred = unet_zoo_amd.SlidingWindowPredict(m, window=(32, 32), overlap=0.5, tile_batch=16, tta=("hflip",))
+        names = ("mask", "prob", "labels", "class_map", "stats", "comps")
+    for tag in ("first", "second", "changed"):
+        if tag == "changed":
+            p = next(m.parameters())
+            with torch.no_grad():
+                p.add_(0.05 * torch.randn(p.shape, generator=torch.Generator().manual_seed(9)).cuda())
+        pred(x)
+        _results(sha, tag, pred, names)
+    sha["captures"], sha["describe"] = str(pred.captures), pred.describe()
+    ops.profile_begin()
+    pred._pipeline(next(iter(pred._graphs.values())))
+    return _take_log()
+
+
+def run_step(cfg, m, x, t, sha):
+    """GraphedStep: two steps; loss, dice and outputs after each, every parameter and buffer after the second"""
+    import torch.nn.functional as F
+    crit = "bce_dice" if cfg["crit"] == "bce_dice" else (lambda o, tt: F.binary_cross_entropy_with_logits(o, tt))
+    step = unet_zoo_amd.GraphedStep(m.train(), crit, lr=1e-2)
+    for tag in ("first", "second"):
+        step(x, t)
+        _results(sha, tag, step, ("loss", "dice", "outputs"))
+    for n, p in m.named_parameters():
+        sha["param/" + n] = _sha(p)
+    sha["describe"] = step.describe()
+    return []
+
+
 def run(cfg):
     from unet_zoo_amd.loss import loss_and_dice
     dtype = torch.bfloat16 if cfg["dtype"] == "bf16" else torch.float32
@@ -114,7 +178,10 @@ def run(cfg):
     x, t = _batch(cfg["b"], cfg["size"])
     sha = {}
     torch.manual_seed(2)
-    if cfg["mode"] == "graphed_eval":
+    if cfg["mode"] in ("graphed_predict", "tiled", "graphed_step"):
+        log = run_predict(cfg, m, x, sha) if cfg["mode"] != "graphed_step" else run_step(cfg, m, x, t, sha)
+        outs = []
+    elif cfg["mode"] == "graphed_eval":
         ev = unet_zoo_amd.GraphedEval(m.eval(), "bce_dice", fold_bn=True)
         ops.profile_begin()
         ev._forward(x)                  # the launches of the captured forward, eagerly (a capture takes no timing events)
@@ -124,6 +191,14 @@ def run(cfg):
         outs = _tensors(ev.outputs)
         sha["loss"], sha["dice"] = _sha(loss), _sha(dice)
         sha["layers"] = f"{ev.folded_layers} folded, {ev.unfolded_layers} unfolded"
+        for tag in ("second", "changed"):       # a plain replay, and one after an in-place parameter change
+            if tag == "changed":
+                p = next(m.parameters())
+                with torch.no_grad():
+                    p.add_(0.05 * torch.randn(p.shape, generator=torch.Generator().manual_seed(9)).cuda())
+            ev(x, t)
+            _results(sha, tag, ev, ("loss", "dice", "outputs"))
+        sha["describe"] = ev.describe()
     elif cfg["mode"] == "eval":
         m.eval()
         ops.profile_begin()

@@ -1,0 +1,203 @@
+"""The capture protocol of every graphed runner, once: ``GraphedStep``, ``GraphedEval``, ``GraphedPredict`` and
+``SlidingWindowPredict`` capture their work into hipGraphs by the rules of this module.
+
+1. One eager pass that changes nothing comes first (``unchanged``): it creates what a capture must not contain -- the
+   kernel-layout weight copies, workspaces, static buffers: allocations and host-to-device copies -- on a side stream, and puts
+   module buffers and the RNG state back.
+2. The pack cache's pointer tables exist before the capture: the captured refresh must find them in place.
+3. No memset node in a capture (``_check_capture``): on this stack it acts in the first replay only.
+4. A graph holds parameter and buffer storage and the tables by address (``GraphedRunner._signature``): when one of them moves
+   every graph is captured again, and when it was storage, the tables are rebuilt from the new addresses first
+   (``PackCache.repoint``).  Who captures once and never again (``GraphedStep``) keeps the tables of its graphs alive.
+"""
+from __future__ import annotations
+
+from contextlib import contextmanager
+from itertools import chain
+from typing import Callable, Dict, Optional, Tuple
+
+import torch
+import torch.nn as nn
+
+from . import _lib as L
+from .engine import Engine
+from .graph import HipModule
+from .loss import MulticlassLoss, RegionLoss, loss_and_dice, loss_and_dice_direct
+
+# hipGraph capture checks only THIS thread's calls: the process-group watchdog thread polls its events concurrently
+# (legal for it, but fatal to a capture in the default "global" mode)
+CAPTURE_MODE = "thread_local"
+
+
+_HIP = None
+
+
+def _memset_nodes(graph: "torch.cuda.CUDAGraph") -> Optional[int]:
+    """number of memset nodes in a captured graph (None when the runtime handle cannot be inspected).  On this stack a
+    memset node of a replayed hipGraph writes its value in the FIRST replay only (tools/graph_canary.py):
+    a library reduction that resets its semaphores with hipMemsetAsync gives right numbers once and silently wrong
+    gradients afterwards -- so a capture that contains one is refused instead of trusted by convention."""
+    global _HIP
+    import ctypes
+    try:
+        raw = graph.raw_cuda_graph()
+        if _HIP is None:
+            _HIP = ctypes.CDLL("libamdhip64.so")
+        n = ctypes.c_size_t(0)
+        if _HIP.hipGraphGetNodes(ctypes.c_void_p(raw), None, ctypes.byref(n)) != 0:
+            return None
+        if n.value == 0:
+            return 0
+        nodes = (ctypes.c_void_p * n.value)()
+        if _HIP.hipGraphGetNodes(ctypes.c_void_p(raw), nodes, ctypes.byref(n)) != 0:
+            return None
+        count = 0
+        for i in range(n.value):
+            t = ctypes.c_int(-1)
+            if _HIP.hipGraphNodeGetType(ctypes.c_void_p(nodes[i]), ctypes.byref(t)) != 0:
+                return None
+            if t.value == 2:          # hipGraphNodeTypeMemset
+                count += 1
+        return count
+    except Exception:                 # noqa: BLE001  (older torch without raw_cuda_graph, no libamdhip64: cannot inspect)
+        return None
+
+
+def _new_graph() -> "torch.cuda.CUDAGraph":
+    try:
+        return torch.cuda.CUDAGraph(keep_graph=True)     # keeps the hipGraph_t so that its nodes can be listed
+    except TypeError:
+        return torch.cuda.CUDAGraph()
+
+
+def _check_capture(graph: "torch.cuda.CUDAGraph", what: str) -> None:
+    n = _memset_nodes(graph)
+    if n:
+        raise RuntimeError(f"GraphedStep: the captured {what} contains {n} memset node(s); on this stack a replayed "
+                           f"memset node acts only once (DESIGN.md 5a) -- a library reduction / zero-fill by "
+                           f"hipMemsetAsync was captured.  Keep it out of the graph (criterion as a callable runs "
+                           f"eagerly) or replace it with a kernel.")
+
+
+def _unwrap(model: nn.Module) -> HipModule:
+    inner = model.module if hasattr(model, "module") and isinstance(model.module, HipModule) else model
+    if not isinstance(inner, HipModule):
+        raise TypeError(f"GraphedStep needs a unet_zoo_amd model (HipModule), got {type(model).__name__}")
+    return inner
+
+
+@contextmanager
+def unchanged(module: nn.Module, device: torch.device):
+    """One eager pass that changes nothing: the body runs on a side stream ordered after the current one; afterwards the
+    streams are joined and the module's buffers (BatchNorm running statistics, counters) and the device's RNG state are what
+    they were before."""
+    saved = [b.detach().clone() for b in module.buffers()]
+    rng = torch.cuda.get_rng_state(device)
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        yield
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize(device)
+    for b, s in zip(module.buffers(), saved):
+        b.copy_(s)
+    torch.cuda.set_rng_state(rng, device)
+    torch.cuda.synchronize(device)
+
+
+def resolve_criterion(criterion) -> Tuple[Optional[Tuple[Callable, Callable]], torch.dtype]:
+    """(fused, target_dtype) of a runner's ``criterion`` argument.  fused: the (autograd, direct) forms of a loss that sits
+    INSIDE the graphs -- "bce_dice" (loss.py's fused kernel) or a RegionLoss / MulticlassLoss instance (uz_region_loss /
+    uz_class_loss: deterministic, no library reduction, graph-safe, they hand over their own gradients) -- or None for any other
+    callable, which is evaluated EAGERLY outside the graphs: library reductions must not be captured on this stack
+    (DESIGN.md 5a).  target_dtype: the static target buffer's -- float32 masks, or what the criterion asks for
+    (MulticlassLoss: int32 class indices)."""
+    target_dtype = getattr(criterion, "target_dtype", torch.float32)
+    if isinstance(criterion, str):
+        if criterion != "bce_dice":
+            raise ValueError(f"unknown built-in criterion {criterion!r}; pass 'bce_dice' or a callable")
+        return (loss_and_dice, loss_and_dice_direct), target_dtype
+    if isinstance(criterion, (RegionLoss, MulticlassLoss)):
+        return (criterion.loss_and_dice, criterion.direct), target_dtype
+    return None, target_dtype
+
+
+def static_copy(t: torch.Tensor, device: torch.device, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """a static input buffer of a captured graph, created from the first batch of its shape: fp32 on the model's device (what
+    `.float().to(device)` of the reference's loops produces) or, for a target, the criterion's target_dtype; later calls copy
+    into it -- host tensors included"""
+    return t.detach().to(device=device, dtype=dtype, copy=True)
+
+
+class GraphedRunner:
+    """One captured graph per input-shape key, invalidated when storage moves: the base of the inference runners.  A subclass
+    states its static buffers, its pipeline and which fields it publishes after a replay; PASS is its own word for what it is."""
+    PASS = "INFERENCE"
+
+    def __init__(self, model: nn.Module, fold_bn: bool):
+        self.model = _unwrap(model)
+        self.fold_bn = bool(fold_bn)
+        self._graphs: Dict[tuple, object] = {}
+        self._sig: Optional[tuple] = None
+        self.captures = 0             # graphs captured so far (a new shape, or storage that moved, adds one)
+
+    # ------------------------------------------------------------------ checks (no GPU call)
+    def _check_model(self, on_gpu: bool = True) -> Optional[torch.device]:
+        m, name = self.model, type(self).__name__
+        if m.training:
+            raise RuntimeError(f"{name} is {self.PASS}: call model.eval() first (GraphedStep is the training step)")
+        if not on_gpu:
+            return None
+        p = next(m.parameters(), None)
+        if p is None or p.device.type != "cuda":
+            raise RuntimeError(f"{name} needs the model on an MI355X ('cuda'): unet_zoo_amd has no CPU path")
+        return p.device
+
+    def _signature(self) -> tuple:
+        """what a captured graph holds by address: parameter / buffer storage and the pack cache's pointer tables"""
+        m = self.model
+        c = m._pack_cache
+        tabs = tuple(t.data_ptr() if t is not None else 0 for t in (c._table, c._table3))
+        return (m.run_dtype, tabs, tuple(t.data_ptr() for t in chain(m.parameters(), m.buffers())))
+
+    # ------------------------------------------------------------------ the forward, as HipModule.forward runs it without a tape
+    def _forward(self, x: torch.Tensor):
+        m = self.model
+        with torch.no_grad():
+            m._pack_cache.refresh(m.run_dtype)
+            eng = Engine(m.run_dtype, x.device, False, False, None, m._pack_cache, False, fold_bn_eval=self.fold_bn)
+            outs = tuple(m.emit(eng, x))
+            eng.finish_forward()
+        self._last_counts = (eng.folded_layers, eng.unfolded_layers)
+        return m.wrap_outputs(tuple(o.detach() for o in outs))
+
+    # ------------------------------------------------------------------ lookup and capture
+    def _lookup(self, key: tuple):
+        """the graph captured for `key`, or None: there is none yet, or what the graphs hold by address moved"""
+        L.load()
+        sig = self._signature()
+        if sig != self._sig:
+            if self._sig is not None and sig[2] != self._sig[2]:
+                # storage moved: the pack cache's tables may still name the old addresses.  (Not when the tables alone moved:
+                # then another runner of this model has just rebuilt them, and rebuilding them again would send that runner
+                # back to its own capture.)  A graph of somebody else that holds the old tables keeps them alive itself.
+                self.model._pack_cache.repoint()
+            self._graphs.clear()
+        return self._graphs.get(key)
+
+    def _capture_graph(self, pipeline: Callable[[], None], what: str, device: torch.device,
+                       warm: Optional[Callable[[], None]] = None) -> "torch.cuda.CUDAGraph":
+        """`pipeline` as a hipGraph named `what`.  `warm` (default: the pipeline itself) is the eager pass in front of it."""
+        m = self.model
+        with unchanged(m, device):
+            (warm or pipeline)()
+            # weight copies registered by that pass leave the pack cache without its pointer tables: build them now
+            # (GraphedStep._setup does the same after its dry run), the captured refresh must find them in place
+            m._pack_cache.refresh(m.run_dtype)
+        graph = _new_graph()
+        with torch.cuda.graph(graph, capture_error_mode=CAPTURE_MODE):
+            pipeline()
+        _check_capture(graph, what)
+        self.captures += 1
+        self._sig = self._signature()      # (the warm-up pass may have built the pack cache's tables)
+        return graph

@@ -29,24 +29,20 @@ shape overwrites them in place, so read (``.item()``) or ``.clone()`` what must 
 
 Parameters are read where they live: the graph holds their addresses and re-packs the kernel-layout weight copies at its
 start (the pack cache's batched launch), so an optimizer step between two calls -- ``GraphedStep`` included -- is seen by the
-next replay.  When parameter or buffer STORAGE moves (``GraphedStep``'s first call gathers the parameters into one flat
-buffer; ``.to()``; ``load_state_dict`` keeps storage) the graphs are captured again.
+next replay; when their storage moves the graphs are captured again.  The capture protocol is ``capture.py``'s.
 
 Module buffers are not modified by a replay, except where the reference's own eval forward modifies them: vnet's
 normalisation uses batch statistics and updates its running statistics in eval mode too, once per call here as there.
 """
 from __future__ import annotations
 
-from itertools import chain
-from typing import Callable, Dict, Optional, Tuple, Union
+from typing import Callable, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
 
-from . import _lib as L
-from .engine import Engine
+from .capture import GraphedRunner, resolve_criterion, static_copy
 from .loss import MulticlassLoss, RegionLoss, loss_and_dice
-from .step import CAPTURE_MODE, _check_capture, _new_graph, _unwrap
 from .surface import SurfaceMetrics
 
 
@@ -55,109 +51,52 @@ class _EvalGraph:
     __slots__ = ("x", "t", "graph", "outputs", "loss", "dice", "folded", "unfolded", "surface")
 
 
-class GraphedEval:
+class GraphedEval(GraphedRunner):
+    PASS = "the EVALUATION pass"
+
     def __init__(self, model: nn.Module, criterion: Union[str, RegionLoss, MulticlassLoss, Callable] = "bce_dice", *, fold_bn: bool = False,
                  surface: Optional[SurfaceMetrics] = None):
-        self.model = _unwrap(model)
+        super().__init__(model, fold_bn)
         if surface is not None and not isinstance(surface, SurfaceMetrics):
             raise TypeError(f"GraphedEval: surface must be a SurfaceMetrics object or None, got {type(surface).__name__}")
         self._surface = surface
         self.surface: Optional[Tuple[torch.Tensor, torch.Tensor]] = None      # the static (out, stats) of the last call
         self.surface_summary: Optional[dict] = None                             # of the last evaluate()
-        if isinstance(criterion, str):
-            if criterion != "bce_dice":
-                raise ValueError(f"unknown built-in criterion {criterion!r}; pass 'bce_dice' or a callable")
-            self._fused_loss = True
-            self._loss_fn = None
-            self._fused = loss_and_dice
-        elif isinstance(criterion, (RegionLoss, MulticlassLoss)):
-            # uz_region_loss / uz_class_loss: deterministic, no library reduction -- inside the graph, where "bce_dice" sits
-            # (two launches: no gradient is asked for); with several ranks each evaluates its own shard, so reduce="batch" is
-            # per shard
-            self._fused_loss = True
-            self._loss_fn = None
-            self._fused = criterion.loss_and_dice
-        else:
-            # evaluated EAGERLY on the static outputs after the replay: library reductions must not be captured on this
-            # stack, exactly as in GraphedStep
-            self._fused_loss = False
-            self._loss_fn = criterion
-        # the static target buffer: float32 masks, or what the criterion asks for (MulticlassLoss: int32 class indices)
-        self._target_dtype = getattr(criterion, "target_dtype", torch.float32)
-        self.fold_bn = bool(fold_bn)
-        self._graphs: Dict[tuple, _EvalGraph] = {}
-        self._sig: Optional[tuple] = None
+        # a fused criterion sits inside the graph, where "bce_dice" sits (two launches: no gradient is asked for, so its
+        # autograd form alone is used); with several ranks each evaluates its own shard, so reduce="batch" is per shard.  Any
+        # other callable is evaluated EAGERLY on the static outputs after the replay, exactly as in GraphedStep
+        fused, self._target_dtype = resolve_criterion(criterion)
+        self._fused_loss = fused is not None
+        self._fused = fused[0] if self._fused_loss else None
+        self._loss_fn = None if self._fused_loss else criterion
         self.loss: Optional[torch.Tensor] = None
         self.dice: Optional[torch.Tensor] = None
         self.outputs = None
         self.folded_layers = 0        # Conv -> BN -> ReLU layers of the last captured forward on the one-launch route
         self.unfolded_layers = 0      # ... and on the two-launch route (fold_bn=True only; both 0 otherwise)
 
-    # ------------------------------------------------------------------ checks (no GPU call)
-    def _check_model(self) -> torch.device:
-        m = self.model
-        if m.training:
-            raise RuntimeError("GraphedEval is the EVALUATION pass: call model.eval() first (GraphedStep is the training step)")
-        p = next(m.parameters(), None)
-        if p is None or p.device.type != "cuda":
-            raise RuntimeError("GraphedEval needs the model on an MI355X ('cuda'): unet_zoo_amd has no CPU path")
-        return p.device
-
-    def _signature(self) -> tuple:
-        """what a captured graph holds by address: parameter / buffer storage and the pack cache's pointer tables"""
-        m = self.model
-        c = m._pack_cache
-        tabs = tuple(t.data_ptr() if t is not None else 0 for t in (c._table, c._table3))
-        return (m.run_dtype, tabs, tuple(t.data_ptr() for t in chain(m.parameters(), m.buffers())))
-
-    # ------------------------------------------------------------------ the forward, as HipModule.forward runs it without a tape
-    def _forward(self, x: torch.Tensor):
-        m = self.model
-        with torch.no_grad():
-            m._pack_cache.refresh(m.run_dtype)
-            eng = Engine(m.run_dtype, x.device, False, False, None, m._pack_cache, False, fold_bn_eval=self.fold_bn)
-            outs = tuple(m.emit(eng, x))
-            eng.finish_forward()
-        self._last_counts = (eng.folded_layers, eng.unfolded_layers)
-        return m.wrap_outputs(tuple(o.detach() for o in outs))
-
     def _capture(self, x: torch.Tensor, t: torch.Tensor) -> _EvalGraph:
-        m = self.model
         g = _EvalGraph()
         g.x, g.t = x, t
-        # one eager forward that changes nothing: creates the kernel-layout weight copies and the pack cache's pointer tables
-        # (host-to-device copies, which a capture must not contain)
-        saved = [b.detach().clone() for b in m.buffers()]
-        rng = torch.cuda.get_rng_state(x.device)
-        side = torch.cuda.Stream(device=x.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            warm = self._forward(x)
+        g.loss = g.dice = None
+
+        def warm():
+            out = self._forward(x)
             if self._fused_loss and self._fused is not loss_and_dice:
                 with torch.no_grad():      # a RegionLoss / MulticlassLoss keeps its workspace (counts, class weights) per shape:
                     # allocated here, outside the capture
-                    self._fused(warm, t)
+                    self._fused(out, t)
             if self._surface is not None:      # its workspace, out and stats of this shape: allocated outside the capture too
-                self._surface(warm, t)
-            del warm
-            # weight copies registered by that forward leave the pack cache without its pointer tables: build them now
-            # (GraphedStep._setup does the same after its dry run), the captured refresh must find them in place
-            m._pack_cache.refresh(m.run_dtype)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize(x.device)
-        for b, s in zip(m.buffers(), saved):
-            b.copy_(s)
-        torch.cuda.set_rng_state(rng, x.device)
-        torch.cuda.synchronize(x.device)
-        g.graph = _new_graph()
-        g.loss = g.dice = None
-        with torch.cuda.graph(g.graph, capture_error_mode=CAPTURE_MODE):
+                self._surface(out, t)
+
+        def pipeline():
             g.outputs = self._forward(g.x)
             if self._fused_loss:
                 with torch.no_grad():      # no gradient: uz_bce_dice / uz_region_loss / uz_class_loss run with dlogits = NULL
                     g.loss, g.dice = self._fused(g.outputs, g.t)
             g.surface = self._surface(g.outputs, g.t) if self._surface is not None else None
-        _check_capture(g.graph, "evaluation graph")
+
+        g.graph = self._capture_graph(pipeline, "evaluation graph", x.device, warm)
         g.folded, g.unfolded = self._last_counts
         return g
 
@@ -165,20 +104,11 @@ class GraphedEval:
     def __call__(self, x: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """(loss, dice) of one batch as 0-dim device tensors; `outputs` holds the model's output container"""
         dev = self._check_model()
-        L.load()
-        sig = self._signature()
-        if sig != self._sig:
-            self._graphs.clear()
         key = (tuple(x.shape), tuple(target.shape))
-        g = self._graphs.get(key)
+        g = self._lookup(key)
         if g is None:
-            # static input buffers of this shape (fp32 on the model's device, what `.float().to(device)` of
-            # training_loop.py:166-167 produces; the target in the criterion's target_dtype where it names one); later calls
-            # copy into them -- host tensors included
-            sx = x.detach().to(device=dev, dtype=torch.float32, copy=True)
-            st = target.detach().to(device=dev, dtype=self._target_dtype, copy=True)
-            g = self._graphs[key] = self._capture(sx, st)
-            self._sig = self._signature()      # (the warm-up forward may have built the pack cache's tables)
+            # static input buffers of this shape (training_loop.py:166-167)
+            g = self._graphs[key] = self._capture(static_copy(x, dev), static_copy(target, dev, self._target_dtype))
         else:                                  # (a fresh capture's static buffers were created from this very batch)
             if x.data_ptr() != g.x.data_ptr():
                 g.x.copy_(x)

@@ -48,77 +48,17 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from .graph import HipModule, PhasedStep
+from .graph import PhasedStep
 from .augment import GpuAugment
-from .loss import MulticlassLoss, RegionLoss, loss_and_dice, loss_and_dice_direct
+from .capture import CAPTURE_MODE, _check_capture, _new_graph, _unwrap, resolve_criterion, static_copy, unchanged
+from .loss import MulticlassLoss, RegionLoss
 from .optim import FlatClipAdamW
-
-# hipGraph capture checks only THIS thread's calls: the process-group watchdog thread polls its events concurrently
-# (legal for it, but fatal to a capture in the default "global" mode)
-CAPTURE_MODE = "thread_local"
-
-
-_HIP = None
-
-
-def _memset_nodes(graph: "torch.cuda.CUDAGraph") -> Optional[int]:
-    """number of memset nodes in a captured graph (None when the runtime handle cannot be inspected).  On this stack a
-    memset node of a replayed hipGraph writes its value in the FIRST replay only (tools/graph_canary.py):
-    a library reduction that resets its semaphores with hipMemsetAsync gives right numbers once and silently wrong
-    gradients afterwards -- so a capture that contains one is refused instead of trusted by convention."""
-    global _HIP
-    import ctypes
-    try:
-        raw = graph.raw_cuda_graph()
-        if _HIP is None:
-            _HIP = ctypes.CDLL("libamdhip64.so")
-        n = ctypes.c_size_t(0)
-        if _HIP.hipGraphGetNodes(ctypes.c_void_p(raw), None, ctypes.byref(n)) != 0:
-            return None
-        if n.value == 0:
-            return 0
-        nodes = (ctypes.c_void_p * n.value)()
-        if _HIP.hipGraphGetNodes(ctypes.c_void_p(raw), nodes, ctypes.byref(n)) != 0:
-            return None
-        count = 0
-        for i in range(n.value):
-            t = ctypes.c_int(-1)
-            if _HIP.hipGraphNodeGetType(ctypes.c_void_p(nodes[i]), ctypes.byref(t)) != 0:
-                return None
-            if t.value == 2:          # hipGraphNodeTypeMemset
-                count += 1
-        return count
-    except Exception:                 # noqa: BLE001  (older torch without raw_cuda_graph, no libamdhip64: cannot inspect)
-        return None
-
-
-def _new_graph() -> "torch.cuda.CUDAGraph":
-    try:
-        return torch.cuda.CUDAGraph(keep_graph=True)     # keeps the hipGraph_t so that its nodes can be listed
-    except TypeError:
-        return torch.cuda.CUDAGraph()
-
-
-def _check_capture(graph: "torch.cuda.CUDAGraph", what: str) -> None:
-    n = _memset_nodes(graph)
-    if n:
-        raise RuntimeError(f"GraphedStep: the captured {what} contains {n} memset node(s); on this stack a replayed "
-                           f"memset node acts only once (DESIGN.md 5a) -- a library reduction / zero-fill by "
-                           f"hipMemsetAsync was captured.  Keep it out of the graph (criterion as a callable runs "
-                           f"eagerly) or replace it with a kernel.")
-
-
-def _unwrap(model: nn.Module) -> HipModule:
-    inner = model.module if hasattr(model, "module") and isinstance(model.module, HipModule) else model
-    if not isinstance(inner, HipModule):
-        raise TypeError(f"GraphedStep needs a unet_zoo_amd model (HipModule), got {type(model).__name__}")
-    return inner
 
 
 class _ShapeGraphs:
     """everything captured for one (input shape, target shape): x / t take the caller's batch, mx / mt are what the model and
     the criterion read -- the same tensors, or the static outputs of the augmentation `aug` captured in front of the model"""
-    __slots__ = ("x", "t", "mx", "mt", "aug", "fwd", "phases", "gouts", "loss", "dice", "outputs", "pool", "ps")
+    __slots__ = ("x", "t", "mx", "mt", "aug", "fwd", "phases", "gouts", "loss", "dice", "outputs", "pool", "ps", "tables")
 
 
 class GraphedStep:
@@ -149,21 +89,11 @@ class GraphedStep:
         if cu_reserve is not None:
             from . import _lib
             _lib.set_cu_reserve(cu_reserve)
-        if isinstance(criterion, str):
-            if criterion != "bce_dice":
-                raise ValueError(f"unknown built-in criterion {criterion!r}; pass 'bce_dice' or a callable")
-            self._fused_loss = True
-            self._loss_fn = lambda out, t: loss_and_dice(out, t)[0]
-            self._fused = (loss_and_dice, loss_and_dice_direct)
-        elif isinstance(criterion, (RegionLoss, MulticlassLoss)):      # fused too: uz_region_loss / uz_class_loss, graph-safe, hand over their own gradients
-            self._fused_loss = True
-            self._loss_fn = lambda out, t: criterion.loss_and_dice(out, t)[0]
-            self._fused = (criterion.loss_and_dice, criterion.direct)
-        else:
-            self._fused_loss = False
-            self._loss_fn = criterion
-        # the static target buffer: float32 masks, or what the criterion asks for (MulticlassLoss: int32 class indices)
-        self._target_dtype = getattr(criterion, "target_dtype", torch.float32)
+        fused, self._target_dtype = resolve_criterion(criterion)
+        self._fused, self._fused_loss = fused, fused is not None
+        # (the lambda must not close over self: in a reference cycle this object and its hipGraphs would wait for the garbage
+        # collector, which may then destroy them in the middle of somebody's capture)
+        self._loss_fn = (lambda out, t: fused[0](out, t)[0]) if fused is not None else criterion
         if augment is not None and not isinstance(augment, GpuAugment):
             raise TypeError(f"augment must be a unet_zoo_amd.GpuAugment, got {type(augment).__name__}")
         self.augment = augment
@@ -200,14 +130,10 @@ class GraphedStep:
         """One eager forward + backward that changes nothing: finds the parameters the graph reaches, the tape
         position that completes each of them, and warms the weight-layout cache."""
         m = self.model
-        saved = [b.detach().clone() for b in m.buffers()]      # BatchNorm running statistics, counters
-        rng = torch.cuda.get_rng_state(x.device)
         for p in m.parameters():
             p.grad = None
         ps = PhasedStep(m, self._loss_fn)
-        side = torch.cuda.Stream(device=x.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
+        with unchanged(m, x.device):
             ps.forward(x, t)
             ps.backward(ps.n_entries, 0, True)
             K = self.n_phases
@@ -216,11 +142,6 @@ class GraphedStep:
             fr = [0.85 * (i + 1) / (K - 1) for i in range(K - 1)] if K > 1 else []
             cuts, groups = ps.plan(fr)
             ps.finish()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize(x.device)
-        for b, s in zip(m.buffers(), saved):
-            b.copy_(s)
-        torch.cuda.set_rng_state(rng, x.device)
         return cuts, groups
 
     def _setup(self, x: torch.Tensor, t: torch.Tensor) -> None:
@@ -325,6 +246,11 @@ class GraphedStep:
             ps.eng.tape.clear()
             ps.eng = None
         g.pool = pool
+        # the graphs hold the pack cache's pointer tables by address, and nothing captures them again: keep THESE tables alive.
+        # The cache drops its own references when it builds new ones (a new weight copy; a graphed inference runner of this
+        # model that saw the storage move, capture.GraphedRunner._lookup), and a replay must not read freed memory.
+        c = self.model._pack_cache
+        g.tables = (c._table, c._table3)
         return g
 
     # ------------------------------------------------------------------ collectives
@@ -399,12 +325,9 @@ class GraphedStep:
         key = (tuple(x.shape), tuple(target.shape))
         g = self._graphs.get(key)
         if g is None:
-            # static input buffers of this shape (fp32 on the model's device, what `.float().to(device)` of
-            # training_loop.py:109-110 produces; the target in the criterion's target_dtype where it names one); later calls
-            # copy into them -- host tensors included
+            # static input buffers of this shape (training_loop.py:109-110)
             dev = next(self.model.parameters()).device
-            sx = x.detach().to(device=dev, dtype=torch.float32, copy=True)
-            st = target.detach().to(device=dev, dtype=self._target_dtype, copy=True)
+            sx, st = static_copy(x, dev), static_copy(target, dev, self._target_dtype)
             aug, mx, mt = None, sx, st
             if self.augment is not None:
                 # the augmentation reads the raw copies and writes static outputs of its own; for the dry run they hold the

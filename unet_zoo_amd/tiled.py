@@ -28,23 +28,22 @@ CAVEAT: a model whose eval forward depends on the batch (vnet normalises with ba
 on ``tile_batch`` and on which tiles share a batch; its running statistics advance once per forward, i.e.
 ``forwards per call`` times per call.
 
-The graphs are captured by ``GraphedPredict``'s rules: an eager warm-up pass on a side stream that restores buffers and the
-RNG state, no memset node in the capture, and a new capture when parameter or buffer storage or the pack cache's tables move
-(the pack cache's pointer tables are rebuilt first) -- an optimizer step between two calls is seen by the next call.
+The graphs are captured by the protocol of ``capture.py``, as ``GraphedPredict``'s are: an optimizer step between two calls is
+seen by the next call.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Sequence
+from typing import Optional, Sequence
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from .capture import static_copy
 from .loss import _maps_of
 from .postprocess import MaskPostprocess, resolve_mode
-from .predict import GraphedPredict
-from .step import CAPTURE_MODE, _check_capture, _new_graph, _unwrap
+from .predict import Predictor
 
 _BLENDS = ("constant", "gaussian")
 
@@ -54,13 +53,12 @@ class _TiledGraph:
     __slots__ = ("x", "plan", "gh", "gw", "views", "tiles", "graph", "prob", "mask", "labels", "class_map", "stats", "comps")
 
 
-class SlidingWindowPredict:
+class SlidingWindowPredict(Predictor):
     def __init__(self, model: nn.Module, *, window, overlap: float = 0.5, blend: str = "gaussian", sigma_scale: float = 0.125,
                  pad_mode: str = "constant", tile_batch: int = 16, tta: Sequence[str] = (), postprocess: Optional[MaskPostprocess] = None,
                  fold_bn: bool = False, mode: str = "auto"):
-        self.model = _unwrap(model)
-        if self.model.training:
-            raise RuntimeError("SlidingWindowPredict is INFERENCE: call model.eval() first (GraphedStep is the training step)")
+        super().__init__(model, tta, postprocess, fold_bn, mode)
+        self._check_model(on_gpu=False)
         if (isinstance(window, (str, bytes)) or not hasattr(window, "__len__") or len(window) != 2
                 or any(isinstance(v, bool) or not isinstance(v, int) or v < 1 for v in window)):
             raise ValueError(f"SlidingWindowPredict: window must be two positive ints (height, width), got {window!r}")
@@ -79,35 +77,9 @@ class SlidingWindowPredict:
         if isinstance(tile_batch, bool) or not isinstance(tile_batch, int) or tile_batch < 1:
             raise ValueError(f"SlidingWindowPredict: tile_batch must be an int >= 1, got {tile_batch!r}")
         self.tile_batch = tile_batch
-        if isinstance(tta, str):
-            raise ValueError(f"SlidingWindowPredict: tta must be a sequence of view names, got the string {tta!r}")
-        self.views = ops.tta_views(tuple(tta))                   # the bit set; the identity is always in it
-        self.n_views = bin(self.views).count("1")
-        if postprocess is not None and not isinstance(postprocess, MaskPostprocess):
-            raise TypeError(f"SlidingWindowPredict: postprocess must be a MaskPostprocess object or None, got {type(postprocess).__name__}")
-        if mode not in ("auto", "binary", "class"):
-            raise ValueError(f"SlidingWindowPredict: mode must be 'auto', 'binary' or 'class', got {mode!r}")
-        self.postprocess, self.mode, self.fold_bn = postprocess, mode, bool(fold_bn)
-        self._graphs: Dict[tuple, _TiledGraph] = {}
-        self._sig: Optional[tuple] = None
-        self.captures = 0             # graphs captured so far (a new shape, or storage that moved, adds one)
         self.plan: Optional[dict] = None
-        self.mask = self.prob = self.labels = self.class_map = self.stats = self.comps = None
 
-    # the model's forward as the prediction graph runs it, and what a captured graph holds by address (predict.py)
-    _forward = GraphedPredict._forward
-    _signature = GraphedPredict._signature
-
-    # ------------------------------------------------------------------ checks and the plan (no GPU call)
-    def _check_model(self) -> torch.device:
-        m = self.model
-        if m.training:
-            raise RuntimeError("SlidingWindowPredict is INFERENCE: call model.eval() first (GraphedStep is the training step)")
-        p = next(m.parameters(), None)
-        if p is None or p.device.type != "cuda":
-            raise RuntimeError("SlidingWindowPredict needs the model on an MI355X ('cuda'): unet_zoo_amd has no CPU path")
-        return p.device
-
+    # ------------------------------------------------------------------ the plan (no GPU call)
     def plan_for(self, shape, channels: int = 1) -> dict:
         """the tiling of an (N, C, H, W) input whose probability map has `channels` channels: host arithmetic alone
         (``uz_tile_plan``); raises on what no call with this shape could run"""
@@ -157,21 +129,9 @@ class SlidingWindowPredict:
                 g.prob = torch.empty((g.x.shape[0], shape[1]) + tuple(g.x.shape[2:]), dtype=torch.float32, device=g.x.device)
             ops.tta_merge(mains, self.views, mode, g.tiles[t0:t0 + tn])
         ops.tile_blend(g.tiles, ys, xs, g.gh, g.gw, g.prob)
-        pp = self.postprocess
-        if pp is not None:
-            g.mask = pp(g.prob, mode="binary" if mode == L.POST_BINARY else "class", from_logits=False)
-            g.labels, g.class_map, g.stats, g.comps = pp.labels, pp.class_map, pp.stats, pp.comps
-        else:
-            cls = mode == L.POST_CLASS
-            if g.mask is None:
-                N, C, H, W = g.prob.shape
-                g.mask = torch.empty((N, C - 1 if cls else C, H, W), dtype=torch.uint8, device=g.x.device)
-                g.class_map = torch.empty((N, H, W), dtype=torch.uint8, device=g.x.device) if cls else None
-            ops.mask_decide(g.prob, mode, 0.5, 1 if cls else 0, g.mask, g.class_map)
-            g.labels = g.stats = g.comps = None
+        self._decide(g, g.prob, mode, 0.5, False)
 
     def _capture(self, x: torch.Tensor, plan: dict) -> _TiledGraph:
-        m = self.model
         g = _TiledGraph()
         g.x, g.plan = x, plan
         th, tw = self.window
@@ -180,27 +140,8 @@ class SlidingWindowPredict:
         tb = min(self.tile_batch, plan["tiles"])
         g.views = [torch.empty((tb, x.shape[1], th, tw), dtype=torch.float32, device=x.device) for _ in range(self.n_views)]
         g.tiles = g.prob = g.mask = g.class_map = None
-        # one eager pass that changes nothing: creates the kernel-layout weight copies, the pack cache's pointer tables, the
-        # static buffers and the post-process plan of this shape (allocations and host-to-device copies, which a capture must
-        # not contain)
-        saved = [b.detach().clone() for b in m.buffers()]
-        rng = torch.cuda.get_rng_state(x.device)
-        side = torch.cuda.Stream(device=x.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self._pipeline(g)
-            m._pack_cache.refresh(m.run_dtype)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize(x.device)
-        for b, s in zip(m.buffers(), saved):
-            b.copy_(s)
-        torch.cuda.set_rng_state(rng, x.device)
-        torch.cuda.synchronize(x.device)
-        g.graph = _new_graph()
-        with torch.cuda.graph(g.graph, capture_error_mode=CAPTURE_MODE):
-            self._pipeline(g)
-        _check_capture(g.graph, "sliding-window prediction graph")
-        self.captures += 1
+        # (the eager pass in front of the capture creates the static buffers and the post-process plan of this shape too)
+        g.graph = self._capture_graph(lambda: self._pipeline(g), "sliding-window prediction graph", x.device)
         return g
 
     # ------------------------------------------------------------------ one batch
@@ -210,43 +151,15 @@ class SlidingWindowPredict:
         g = self._graphs.get(key)
         plan = g.plan if g is not None else self.plan_for(key)   # (raises before any GPU call)
         dev = self._check_model()
-        L.load()
-        sig = self._signature()
-        if sig != self._sig:
-            if self._sig is not None:
-                self.model._pack_cache.repoint()     # storage moved: the pack cache's tables still name the old addresses
-            self._graphs.clear()
-            g = None
+        g = self._lookup(key)
         if g is None:
-            sx = x.detach().to(device=dev, dtype=torch.float32, copy=True).contiguous()
-            g = self._graphs[key] = self._capture(sx, plan)
-            self._sig = self._signature()      # (the warm-up pass may have built the pack cache's tables)
-        elif x.data_ptr() != g.x.data_ptr():
-            g.x.copy_(x)
-        g.graph.replay()
-        self.mask, self.prob, self.plan = g.mask, g.prob, g.plan
-        self.labels, self.class_map, self.stats, self.comps = g.labels, g.class_map, g.stats, g.comps
-        return g.mask
-
-    def check(self) -> None:
-        """the post-process's error words of the last call, read on the host (MaskPostprocess.check)"""
-        if self.postprocess is not None and self.stats is not None:
-            err = self.stats[..., 6]
-            if bool((err != 0).any().item()):
-                raise RuntimeError("SlidingWindowPredict: a bounded union-find loop of the post-process ran out; the masks are undefined")
-
-    # ------------------------------------------------------------------ one pass over a loader
-    def predict(self, loader):
-        """yields a CLONED mask per batch; a batch is an image tensor or an (image, ...) sequence"""
-        for batch in loader:
-            x = batch if isinstance(batch, torch.Tensor) else batch[0]
-            yield self(x).clone()
+            g = self._graphs[key] = self._capture(static_copy(x, dev).contiguous(), plan)
+            x = g.x                            # (created from this very batch: nothing to copy)
+        self.plan = g.plan
+        return self._replay(g, x)
 
     def describe(self) -> str:
-        names = [n for n, b in L.TTA_VIEWS.items() if self.views & b]
-        tail = "postproc" if self.postprocess is not None else "decide"
-        fold = ", eval BatchNorm folded into the convolution epilogues" if self.fold_bn else ""
-        flip = "flip+" if self.n_views > 1 else ""
-        return (f"hipGraph(tile batches of {self.tile_batch} x (gather+{flip}{self.n_views} x fwd+merge) + blend+{tail}) per input shape, "
+        fwd, tail, views = self._describe()
+        return (f"hipGraph(tile batches of {self.tile_batch} x (gather+{fwd}) + blend+{tail}) per input shape, "
                 f"window {self.window[0]} x {self.window[1]}, overlap {self.overlap:g}, {self.blend} weights, {self.pad_mode} padding, "
-                f"views {'/'.join(names)}{fold}")
+                f"{views}")
