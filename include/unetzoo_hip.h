@@ -1109,6 +1109,58 @@ int uz_surface_metrics(const uz_surface_desc* d, const float* logits, const void
                        void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Boundary loss (Kervadec et al., "Boundary loss for highly unbalanced segmentation") on top of a base loss whose value
+ * and gradients exist already: the exact signed Euclidean distance transform of the target, dense, and the mean of
+ * probability x signed distance over several output maps.  uz_boundary_loss.hip
+ * Per plane with target mask G on H x W, sd2 is an INTEGER:
+ *   sd2(p) = +min over g in G of |p - g|^2 for p outside G, -min over q outside G of |p - q|^2 for p in G, and 0
+ *            everywhere when G is empty or the whole plane.  Pixels outside the picture do not exist.
+ *   phi(p) = spacing sqrt(sd2) where sd2 > 0, -spacing (sqrt(-sd2) - 1) where sd2 < 0, 0 where sd2 = 0
+ *            -- edt(~G) ~G - (edt(G) - 1) G of scipy.ndimage.distance_transform_edt
+ * UZ_BOUNDARY_BINARY: logits and target (N, C, H, W) fp32; G = target > 0.5, every (image, channel) a plane: M = N C;
+ *   p = sigmoid(x);  B = sum p phi / (N C H W);  dB/dx = phi p (1 - p) / (N C H W).
+ * UZ_BOUNDARY_CLASS : logits (N, C, H, W) fp32 with C = K classes, target (N, H, W) int32 labels y; G_c = (y == c) for
+ *   c in Cset = first_class .. K - 1: M = N (K - first_class), plane n * (K - first_class) + (c - first_class).  A pixel
+ *   whose label is ignore_index or outside [0, K) is in no G_c (for the transform it is complement), adds nothing to the sum
+ *   and has zero gradient.  p = softmax_K(x);  B = sum over valid pixels and Cset of p_c phi_c / (N |Cset| H W);
+ *   dB/dx_k = p_k (phit_k - sum_c p_c phit_c) / (N |Cset| H W) with phit_c = phi_c in Cset, 0 otherwise.
+ * scales = {weight, base_scale}, two floats ON THE DEVICE, and base_loss, one float on the device, are read by the kernels:
+ *   out[0] = base_scale * base_loss + weight * sum_m items[m].weight * B_m;   out[1] = B of map metric_item
+ *   items[m].dlogits (nullable) holds d(base_loss)/d(logits) on entry and is rewritten in place:
+ *   dl <- base_scale * dl + weight * items[m].weight * dB/dx
+ * sd2 (M, H, W) int32 is an OUTPUT of the call, computed once and shared by all maps; phi is formed from it on the fly.
+ * One call is FIVE launches whatever n_items is (rows, planes, columns, loss, finalize), no allocation, no memset, no host
+ * read; float64 sums in a fixed order: two calls on the same inputs give the same bits.  `items` is a HOST array copied
+ * into the kernel arguments.  uz_boundary_grid() returns the workgroups of the column pass and (units, nullable) the units
+ * they share out (a unit: 256 consecutive pixels of one plane): units > workgroups means workgroups walk.
+ * UZ_EINVAL before any launch: null descriptor / pointer (dlogits may be null), unknown mode, n_items outside
+ * [1, UZ_CLASS_MAX_ITEMS], N, C, H or W < 1, H or W > 4096, in the class mode K outside [2, UZ_CLASS_MAX_K] or first_class
+ * outside [0, K), metric_item outside [0, n_items), spacing not positive and finite, N C H W >= 2^31, 2^30 or more units,
+ * an item's weight negative, tensors misaligned (4 bytes; workspace 16), or a written buffer (out, sd2, workspace, dlogits)
+ * overlapping any other buffer of the call. */
+#define UZ_BOUNDARY_BINARY 0
+#define UZ_BOUNDARY_CLASS 1
+typedef struct uz_boundary_item {
+  const float* logits;
+  float* dlogits; /* nullable; in: the base loss's gradient, out: the combined one */
+  float weight;
+} uz_boundary_item;
+typedef struct uz_boundary_desc {
+  int mode; /* UZ_BOUNDARY_* */
+  int n_items;
+  int N, C, H, W;   /* C: channels (binary) or classes K (class mode) */
+  int first_class;  /* class mode: the first class of Cset (1 leaves the background out) */
+  int ignore_index; /* class mode */
+  int metric_item;
+  float spacing; /* isotropic pixel spacing */
+} uz_boundary_desc;
+long long uz_boundary_workspace_bytes(const uz_boundary_desc* d); /* < 0: refused */
+int uz_boundary_grid(const uz_boundary_desc* d, int* units /* nullable */);
+int uz_boundary_loss(const uz_boundary_desc* d, const uz_boundary_item* items, const void* target,
+                     const float* scales /* device: weight, base_scale */, const float* base_loss /* device */,
+                     float* out /* 2 */, int* sd2 /* M * H * W, an output */, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Mask post-processing, per (image, plane), every result an integer that scipy.ndimage gives too.  uz_postproc.hip
  * UZ_POST_BINARY: x (N, C, H, W) fp32; plane = x > thr, every channel a plane: P = C.  Logits with thr = 0 or
  *   probabilities with thr = 0.5.

@@ -58,6 +58,7 @@ EXPORTS = (
     "uz_class_loss_workspace_bytes", "uz_class_loss",
     "uz_augment_params", "uz_augment_grid", "uz_augment_apply",
     "uz_surface_workspace_bytes", "uz_surface_grid", "uz_surface_metrics",
+    "uz_boundary_workspace_bytes", "uz_boundary_grid", "uz_boundary_loss",
     "uz_postproc_workspace_bytes", "uz_postproc_grid", "uz_postproc",
     "uz_tta_num_views", "uz_flip_views", "uz_tta_merge", "uz_mask_decide",
     "uz_tile_plan", "uz_tile_gather", "uz_tile_blend",
@@ -200,6 +201,21 @@ class SurfaceDesc(Structure):
     """uz_surface_desc"""
     _fields_ = [(n, c_int) for n in ("mode", "N", "C", "H", "W", "first_class", "ignore_index", "reserved")] \
         + [("q", c_double), ("spacing", c_double)]
+
+
+BOUNDARY_BINARY, BOUNDARY_CLASS = 0, 1
+BOUNDARY_MAX_HW = 4096
+
+
+class BoundaryItem(Structure):
+    """uz_boundary_item: one output map of a uz_boundary_loss call"""
+    _fields_ = [("logits", c_void_p), ("dlogits", c_void_p), ("weight", c_float)]
+
+
+class BoundaryDesc(Structure):
+    """uz_boundary_desc"""
+    _fields_ = [(n, c_int) for n in ("mode", "n_items", "N", "C", "H", "W", "first_class", "ignore_index", "metric_item")] \
+        + [("spacing", c_float)]
 
 
 POST_BINARY, POST_CLASS = 0, 1
@@ -421,6 +437,9 @@ def load():
     lib.uz_surface_workspace_bytes.argtypes = [POINTER(SurfaceDesc)]
     lib.uz_surface_grid.argtypes = [POINTER(SurfaceDesc), POINTER(c_int)]
     lib.uz_surface_metrics.argtypes = [POINTER(SurfaceDesc), vp, vp, vp, vp, vp, vp]
+    lib.uz_boundary_workspace_bytes.argtypes = [POINTER(BoundaryDesc)]
+    lib.uz_boundary_grid.argtypes = [POINTER(BoundaryDesc), POINTER(c_int)]
+    lib.uz_boundary_loss.argtypes = [POINTER(BoundaryDesc), POINTER(BoundaryItem), vp, vp, vp, vp, vp, vp, vp]
     lib.uz_postproc_workspace_bytes.argtypes = [POINTER(PostprocDesc)]
     lib.uz_postproc_grid.argtypes = [POINTER(PostprocDesc), POINTER(c_int)]
     lib.uz_postproc.argtypes = [POINTER(PostprocDesc), vp, vp, vp, vp, vp, vp, vp, vp]
@@ -504,6 +523,28 @@ def surface_metrics(desc: "SurfaceDesc", logits: torch.Tensor, target: torch.Ten
     """uz_surface_metrics() on the current stream: seven launches, no allocation, no host read"""
     check(load().uz_surface_metrics(ctypes.byref(desc), logits.data_ptr(), target.data_ptr(), out.data_ptr(), stats.data_ptr(),
                                     workspace.data_ptr(), stream_ptr()), "uz_surface_metrics")
+
+
+def boundary_workspace_bytes(desc: "BoundaryDesc") -> int:
+    """uz_boundary_workspace_bytes(): bytes of workspace a uz_boundary_loss call with this descriptor needs"""
+    return check_count(load().uz_boundary_workspace_bytes(ctypes.byref(desc)), "uz_boundary_workspace_bytes")
+
+
+def boundary_grid(desc: "BoundaryDesc") -> tuple:
+    """uz_boundary_grid(): (workgroups, units) of the column pass of uz_boundary_loss for this descriptor"""
+    units = c_int(0)
+    grid = check_count(load().uz_boundary_grid(ctypes.byref(desc), ctypes.byref(units)), "uz_boundary_grid")
+    return grid, units.value
+
+
+def boundary_loss(desc: "BoundaryDesc", items, target: torch.Tensor, scales: torch.Tensor, base_loss: torch.Tensor,
+                  out2: torch.Tensor, sd2: torch.Tensor, workspace: torch.Tensor) -> None:
+    """uz_boundary_loss() on the current stream: `items` is a ctypes array of BoundaryItem (a HOST table, copied into the
+    kernel arguments), scales the (weight, base_scale) pair and base_loss the base criterion's value ON THE DEVICE, out2 a
+    2-element fp32 device tensor (loss, boundary term of the main map), sd2 the int32 (M, H, W) transform it writes.  Five
+    launches, no allocation, no host read.  Every call of the loss goes through here."""
+    check(load().uz_boundary_loss(ctypes.byref(desc), items, target.data_ptr(), scales.data_ptr(), base_loss.data_ptr(),
+                                  out2.data_ptr(), sd2.data_ptr(), workspace.data_ptr(), stream_ptr()), "uz_boundary_loss")
 
 
 def postproc_workspace_bytes(desc: "PostprocDesc") -> int:

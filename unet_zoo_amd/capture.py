@@ -22,6 +22,7 @@ import torch.nn as nn
 from . import _lib as L
 from .engine import Engine
 from .graph import HipModule
+from .boundary import BoundaryLoss
 from .loss import MulticlassLoss, RegionLoss, loss_and_dice, loss_and_dice_direct
 
 # hipGraph capture checks only THIS thread's calls: the process-group watchdog thread polls its events concurrently
@@ -117,7 +118,7 @@ def resolve_criterion(criterion) -> Tuple[Optional[Tuple[Callable, Callable]], t
         if criterion != "bce_dice":
             raise ValueError(f"unknown built-in criterion {criterion!r}; pass 'bce_dice' or a callable")
         return (loss_and_dice, loss_and_dice_direct), target_dtype
-    if isinstance(criterion, (RegionLoss, MulticlassLoss)):
+    if isinstance(criterion, (RegionLoss, MulticlassLoss, BoundaryLoss)):
         return (criterion.loss_and_dice, criterion.direct), target_dtype
     return None, target_dtype
 

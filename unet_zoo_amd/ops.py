@@ -1696,6 +1696,31 @@ def surface_metrics(desc: "L.SurfaceDesc", logits: torch.Tensor, target: torch.T
         L.surface_metrics(desc, logits, target, out, stats, workspace)
 
 
+# ---- BoundaryLoss: signed distance transform of the target + the boundary term (uz_boundary_loss.hip) -------------------------
+def boundary_grid(desc: "L.BoundaryDesc") -> tuple:
+    """(workgroups, units) of the column pass of uz_boundary_loss for this descriptor: units > workgroups means workgroups
+    walk"""
+    return L.boundary_grid(desc)
+
+
+def boundary_loss(desc: "L.BoundaryDesc", items, target: torch.Tensor, scales: torch.Tensor, base_loss: torch.Tensor,
+                  out2: torch.Tensor, sd2: torch.Tensor, workspace: torch.Tensor) -> None:
+    """out2 = (base_scale * base_loss + weight * sum_m ow_m B_m, B_main) and sd2 (M, H, W) int32 <- the maps of `items`
+    (fp32, (N, C, H, W)) against target: fp32 (N, C, H, W) masks (UZ_BOUNDARY_BINARY) or int32 (N, H, W) labels
+    (UZ_BOUNDARY_CLASS); the gradient buffers of `items` are rewritten in place; five launches"""
+    L.require_cuda(target, scales, base_loss, out2, sd2, workspace)
+    for t in (target, scales, base_loss, out2, sd2, workspace):
+        assert t.is_contiguous()
+    cls = desc.mode == L.BOUNDARY_CLASS
+    M = desc.N * ((desc.C - desc.first_class) if cls else desc.C)
+    assert scales.dtype == base_loss.dtype == out2.dtype == torch.float32 and sd2.dtype == torch.int32
+    assert target.dtype == (torch.int32 if cls else torch.float32)
+    assert tuple(target.shape) == ((desc.N, desc.H, desc.W) if cls else (desc.N, desc.C, desc.H, desc.W))
+    assert scales.numel() == 2 and out2.numel() == 2 and base_loss.numel() == 1 and tuple(sd2.shape) == (M, desc.H, desc.W)
+    with _Timed("boundary_loss", 0.0, 4.0 * (target.numel() + sd2.numel() + 2 * desc.n_items * desc.N * desc.C * desc.H * desc.W)):
+        L.boundary_loss(desc, items, target, scales, base_loss, out2, sd2, workspace)
+
+
 # ---- MaskPostprocess / GraphedPredict: components, hole filling, flip TTA (uz_postproc.hip, uz_tta.hip) -----------------------
 def postproc_grid(desc: "L.PostprocDesc") -> tuple:
     """(workgroups, units) of the per-unit launches of uz_postproc for this descriptor: units > workgroups means workgroups
