@@ -1161,6 +1161,69 @@ int uz_boundary_loss(const uz_boundary_desc* d, const uz_boundary_item* items, c
                      float* out /* 2 */, int* sd2 /* M * H * W, an output */, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Lovasz hinge / Lovasz-softmax (Berman, Triggs, Blaschko, "The Lovasz-Softmax loss", CVPR 2018) on top of a base loss whose
+ * value and gradients exist already: a segmented STABLE sort of the pixel errors and a scan over the sorted membership
+ * bits.  uz_lovasz_loss.hip
+ * A segment is a list of (error e, membership bit b).  The elements with e > 0 are ranked 0, 1, ... by descending e, ties by
+ * ascending position; an element with e <= 0 has rank -1, adds nothing and has zero gradient.  With G members (b = 1) in
+ * the whole segment, c members among ranks 0 .. r and n = r + 1 - c, the element at rank r weighs
+ *   g = 1 / (G + n) if b = 1,  (G - c) / ((G + n - 1) (G + n)) if b = 0,  1 at rank 0 of a segment with G = 0
+ * (the difference J_r - J_(r-1) of J_r = 1 - (G - c) / (G + n)), and the segment's value is L = sum over ranks of e g.
+ * UZ_LOVASZ_BINARY: logits and target (N, C, H, W) fp32; b = target > 0.5, s = +1 where b else -1, e = 1 - x s in fp32.
+ *   per_image: a segment per (image, channel) in row-major pixel order, S = N C of length H W; otherwise a segment per
+ *   channel over the batch in image-major order, S = C of length N H W.  V = mean of L over the S segments;
+ *   dV/dx = -s g / S at a ranked pixel.
+ * UZ_LOVASZ_CLASS : logits (N, C, H, W) fp32 with C = K classes, target (N, H, W) int32 labels y; p = softmax_K(x), for
+ *   class c: b = (y == c), e = |b - p_c|.  A pixel whose label is ignore_index or outside [0, K) is in no segment (e = 0,
+ *   rank -1, no member, zero gradient on all K logits).  per_image: a segment per (image, class), segment n K + c;
+ *   otherwise per class over the batch.  With P_l the classes that have a member in line l (an image, or the batch), or all
+ *   K with UZ_LOVASZ_ALL:  V = (1 / lines) sum_l (1 / |P_l|) sum_{c in P_l} L_{l,c}; a line with empty P_l adds 0.
+ *   dV/dx_k = p_k (d_k - sum_c p_c d_c) with d_c = sign(p_c - b) g / (lines |P_l|) at a ranked element, 0 otherwise.
+ * scales = {weight, base_scale}, two floats ON THE DEVICE, and base_loss, one float on the device, are read by the kernels:
+ *   out[0] = base_scale * base_loss + weight * sum_m items[m].weight * V_m;   out[1] = V of map main_item
+ *   items[m].dlogits (nullable) holds d(base_loss)/d(logits) on entry and is rewritten in place:
+ *   dl <- base_scale * dl + weight * items[m].weight * dV/dx
+ * errors (S, length) fp32 and ranks (S, length) int32 are OUTPUTS of the call, of map main_item.  Every map is sorted on its
+ * own, all of them in the same launches: the workspace grows linearly with n_items (16 bytes per element of every map for
+ * the two key / value buffers, plus about 1 byte per element for the digit counts).
+ * One call is 18 launches, 19 when a map has a gradient buffer, whatever n_items and the data are: keys, segments, 4 x (hist,
+ * rowscan, scatter) of a least-significant-digit radix sort with 8-bit digits, bits, scan, [grad,] finalize.  No
+ * allocation, no memset, no host read, no float atomics, no waiting between workgroups; float64 sums in a fixed order and
+ * a scatter whose positions do not depend on arrival order: two calls on the same inputs give the same bits, `ranks`
+ * included.  `items` is a HOST array copied into the kernel arguments.  uz_lovasz_grid() returns the workgroups of the passes
+ * over (segment, tile) units and (units, nullable) the units they share out (a unit: 1024 consecutive elements of one
+ * segment): units > workgroups means workgroups walk.
+ * UZ_EINVAL before any launch: null descriptor / pointer (dlogits may be null), unknown mode or classes mode, n_items outside
+ * [1, UZ_CLASS_MAX_ITEMS], N, C, H or W < 1, in the class mode K outside [2, UZ_CLASS_MAX_K], main_item outside
+ * [0, n_items), a segment longer than 2^22, more than 2^28 elements in all maps, an item's weight negative, tensors
+ * misaligned (4 bytes; workspace 16), or a written buffer (out, errors, ranks, workspace, dlogits) overlapping any other
+ * buffer of the call. */
+#define UZ_LOVASZ_BINARY 0
+#define UZ_LOVASZ_CLASS 1
+#define UZ_LOVASZ_PRESENT 0
+#define UZ_LOVASZ_ALL 1
+typedef struct uz_lovasz_item {
+  const float* logits;
+  float* dlogits; /* nullable; in: the base loss's gradient, out: the combined one */
+  float weight;
+} uz_lovasz_item;
+typedef struct uz_lovasz_desc {
+  int mode; /* UZ_LOVASZ_BINARY / UZ_LOVASZ_CLASS */
+  int n_items;
+  int N, C, H, W;   /* C: channels (binary) or classes K (class mode) */
+  int per_image;    /* 0: one segment per channel / class over the whole batch */
+  int classes;      /* class mode: UZ_LOVASZ_PRESENT / UZ_LOVASZ_ALL */
+  int ignore_index; /* class mode */
+  int main_item;
+} uz_lovasz_desc;
+long long uz_lovasz_workspace_bytes(const uz_lovasz_desc* d); /* < 0: refused */
+int uz_lovasz_grid(const uz_lovasz_desc* d, int* units /* nullable */);
+int uz_lovasz_loss(const uz_lovasz_desc* d, const uz_lovasz_item* items, const void* target,
+                   const float* scales /* device: weight, base_scale */, const float* base_loss /* device */,
+                   float* out /* 2 */, float* errors /* S * length, an output */, int* ranks /* S * length, an output */,
+                   void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Mask post-processing, per (image, plane), every result an integer that scipy.ndimage gives too.  uz_postproc.hip
  * UZ_POST_BINARY: x (N, C, H, W) fp32; plane = x > thr, every channel a plane: P = C.  Logits with thr = 0 or
  *   probabilities with thr = 0.5.

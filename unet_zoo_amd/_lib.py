@@ -59,6 +59,7 @@ EXPORTS = (
     "uz_augment_params", "uz_augment_grid", "uz_augment_apply",
     "uz_surface_workspace_bytes", "uz_surface_grid", "uz_surface_metrics",
     "uz_boundary_workspace_bytes", "uz_boundary_grid", "uz_boundary_loss",
+    "uz_lovasz_workspace_bytes", "uz_lovasz_grid", "uz_lovasz_loss",
     "uz_postproc_workspace_bytes", "uz_postproc_grid", "uz_postproc",
     "uz_tta_num_views", "uz_flip_views", "uz_tta_merge", "uz_mask_decide",
     "uz_tile_plan", "uz_tile_gather", "uz_tile_blend",
@@ -216,6 +217,22 @@ class BoundaryDesc(Structure):
     """uz_boundary_desc"""
     _fields_ = [(n, c_int) for n in ("mode", "n_items", "N", "C", "H", "W", "first_class", "ignore_index", "metric_item")] \
         + [("spacing", c_float)]
+
+
+LOVASZ_BINARY, LOVASZ_CLASS = 0, 1
+LOVASZ_PRESENT, LOVASZ_ALL = 0, 1
+LOVASZ_MAX_SEGMENT = 1 << 22
+LOVASZ_MAX_ELEMENTS = 1 << 28
+
+
+class LovaszItem(Structure):
+    """uz_lovasz_item: one output map of a uz_lovasz_loss call"""
+    _fields_ = [("logits", c_void_p), ("dlogits", c_void_p), ("weight", c_float)]
+
+
+class LovaszDesc(Structure):
+    """uz_lovasz_desc"""
+    _fields_ = [(n, c_int) for n in ("mode", "n_items", "N", "C", "H", "W", "per_image", "classes", "ignore_index", "main_item")]
 
 
 POST_BINARY, POST_CLASS = 0, 1
@@ -440,6 +457,9 @@ def load():
     lib.uz_boundary_workspace_bytes.argtypes = [POINTER(BoundaryDesc)]
     lib.uz_boundary_grid.argtypes = [POINTER(BoundaryDesc), POINTER(c_int)]
     lib.uz_boundary_loss.argtypes = [POINTER(BoundaryDesc), POINTER(BoundaryItem), vp, vp, vp, vp, vp, vp, vp]
+    lib.uz_lovasz_workspace_bytes.argtypes = [POINTER(LovaszDesc)]
+    lib.uz_lovasz_grid.argtypes = [POINTER(LovaszDesc), POINTER(c_int)]
+    lib.uz_lovasz_loss.argtypes = [POINTER(LovaszDesc), POINTER(LovaszItem), vp, vp, vp, vp, vp, vp, vp, vp]
     lib.uz_postproc_workspace_bytes.argtypes = [POINTER(PostprocDesc)]
     lib.uz_postproc_grid.argtypes = [POINTER(PostprocDesc), POINTER(c_int)]
     lib.uz_postproc.argtypes = [POINTER(PostprocDesc), vp, vp, vp, vp, vp, vp, vp, vp]
@@ -545,6 +565,29 @@ def boundary_loss(desc: "BoundaryDesc", items, target: torch.Tensor, scales: tor
     launches, no allocation, no host read.  Every call of the loss goes through here."""
     check(load().uz_boundary_loss(ctypes.byref(desc), items, target.data_ptr(), scales.data_ptr(), base_loss.data_ptr(),
                                   out2.data_ptr(), sd2.data_ptr(), workspace.data_ptr(), stream_ptr()), "uz_boundary_loss")
+
+
+def lovasz_workspace_bytes(desc: "LovaszDesc") -> int:
+    """uz_lovasz_workspace_bytes(): bytes of workspace a uz_lovasz_loss call with this descriptor needs"""
+    return check_count(load().uz_lovasz_workspace_bytes(ctypes.byref(desc)), "uz_lovasz_workspace_bytes")
+
+
+def lovasz_grid(desc: "LovaszDesc") -> tuple:
+    """uz_lovasz_grid(): (workgroups, units) of the passes over (segment, tile) units of uz_lovasz_loss for this descriptor"""
+    units = c_int(0)
+    grid = check_count(load().uz_lovasz_grid(ctypes.byref(desc), ctypes.byref(units)), "uz_lovasz_grid")
+    return grid, units.value
+
+
+def lovasz_loss(desc: "LovaszDesc", items, target: torch.Tensor, scales: torch.Tensor, base_loss: torch.Tensor,
+                out2: torch.Tensor, errors: torch.Tensor, ranks: torch.Tensor, workspace: torch.Tensor) -> None:
+    """uz_lovasz_loss() on the current stream: `items` is a ctypes array of LovaszItem (a HOST table, copied into the kernel
+    arguments), scales the (weight, base_scale) pair and base_loss the base criterion's value ON THE DEVICE, out2 a 2-element
+    fp32 device tensor (loss, V of the main map), errors (fp32) and ranks (int32) the (segments, length) outputs of the main
+    map.  18 or 19 launches, no allocation, no host read.  Every call of the loss goes through here."""
+    check(load().uz_lovasz_loss(ctypes.byref(desc), items, target.data_ptr(), scales.data_ptr(), base_loss.data_ptr(),
+                                out2.data_ptr(), errors.data_ptr(), ranks.data_ptr(), workspace.data_ptr(), stream_ptr()),
+          "uz_lovasz_loss")
 
 
 def postproc_workspace_bytes(desc: "PostprocDesc") -> int:

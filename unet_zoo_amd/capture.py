@@ -24,6 +24,7 @@ from .engine import Engine
 from .graph import HipModule
 from .boundary import BoundaryLoss
 from .loss import MulticlassLoss, RegionLoss, loss_and_dice, loss_and_dice_direct
+from .lovasz import LovaszLoss
 
 # hipGraph capture checks only THIS thread's calls: the process-group watchdog thread polls its events concurrently
 # (legal for it, but fatal to a capture in the default "global" mode)
@@ -118,7 +119,7 @@ def resolve_criterion(criterion) -> Tuple[Optional[Tuple[Callable, Callable]], t
         if criterion != "bce_dice":
             raise ValueError(f"unknown built-in criterion {criterion!r}; pass 'bce_dice' or a callable")
         return (loss_and_dice, loss_and_dice_direct), target_dtype
-    if isinstance(criterion, (RegionLoss, MulticlassLoss, BoundaryLoss)):
+    if isinstance(criterion, (RegionLoss, MulticlassLoss, BoundaryLoss, LovaszLoss)):
         return (criterion.loss_and_dice, criterion.direct), target_dtype
     return None, target_dtype
 

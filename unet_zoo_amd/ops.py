@@ -1721,6 +1721,36 @@ def boundary_loss(desc: "L.BoundaryDesc", items, target: torch.Tensor, scales: t
         L.boundary_loss(desc, items, target, scales, base_loss, out2, sd2, workspace)
 
 
+# ---- LovaszLoss: segmented stable sort of the pixel errors + the Jaccard-difference scan (uz_lovasz_loss.hip) -----------------
+def lovasz_grid(desc: "L.LovaszDesc") -> tuple:
+    """(workgroups, units) of the passes over (segment, tile) units of uz_lovasz_loss for this descriptor: units > workgroups
+    means workgroups walk"""
+    return L.lovasz_grid(desc)
+
+
+def lovasz_loss(desc: "L.LovaszDesc", items, target: torch.Tensor, scales: torch.Tensor, base_loss: torch.Tensor,
+                out2: torch.Tensor, errors: torch.Tensor, ranks: torch.Tensor, workspace: torch.Tensor) -> None:
+    """out2 = (base_scale * base_loss + weight * sum_m ow_m V_m, V_main), errors / ranks (segments, length) of the main map <-
+    the maps of `items` (fp32, (N, C, H, W)) against target: fp32 (N, C, H, W) masks (UZ_LOVASZ_BINARY) or int32 (N, H, W)
+    labels (UZ_LOVASZ_CLASS); the gradient buffers of `items` are rewritten in place; 18 or 19 launches"""
+    L.require_cuda(target, scales, base_loss, out2, errors, ranks, workspace)
+    for t in (target, scales, base_loss, out2, errors, ranks, workspace):
+        assert t.is_contiguous()
+    cls = desc.mode == L.LOVASZ_CLASS
+    hw = desc.H * desc.W
+    seg = (desc.N * desc.C, hw) if desc.per_image else (desc.C, desc.N * hw)
+    assert scales.dtype == base_loss.dtype == out2.dtype == errors.dtype == torch.float32 and ranks.dtype == torch.int32
+    assert target.dtype == (torch.int32 if cls else torch.float32)
+    assert tuple(target.shape) == ((desc.N, desc.H, desc.W) if cls else (desc.N, desc.C, desc.H, desc.W))
+    assert scales.numel() == 2 and out2.numel() == 2 and base_loss.numel() == 1
+    assert tuple(errors.shape) == seg and tuple(ranks.shape) == seg
+    elems = desc.n_items * desc.N * desc.C * hw
+    # per element of every map: logits 4 + gradient read and written 8 + key and value written 8 + four passes of (hist reads
+    # the key 4, scatter reads and writes key and value 16) + bits 4 + scan reads 8 and writes g and the rank 8 = 120 bytes
+    with _Timed("lovasz_loss", 0.0, 4.0 * target.numel() + 120.0 * elems):
+        L.lovasz_loss(desc, items, target, scales, base_loss, out2, errors, ranks, workspace)
+
+
 # ---- MaskPostprocess / GraphedPredict: components, hole filling, flip TTA (uz_postproc.hip, uz_tta.hip) -----------------------
 def postproc_grid(desc: "L.PostprocDesc") -> tuple:
     """(workgroups, units) of the per-unit launches of uz_postproc for this descriptor: units > workgroups means workgroups
