@@ -1066,6 +1066,63 @@ int uz_augment_apply(const uz_augment_desc* d, const float* image, const void* m
                      float* image_out, void* mask_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Patch training from a pool of pictures that stays on the device: foreground-aware patch coordinates from uniform draws,
+ * and the patches.  uz_patch.hip
+ * Pool: image (M, C, H, W) fp32 or uint8 (image_kind), C in 1..4; mask (mask_kind) none, fp32 (M, Cm, H, W) with Cm in 1..8, or
+ *   int32 class indices (M, H, W).  Foreground planes, P of them: an fp32 mask has P = Cm, plane c is mask[m, c] > 0.5; labels
+ *   have P = num_classes - 1 <= 8, plane p is label == p + 1 (class 0, an ignore index and every other value are background);
+ *   no mask: P = 0.  A batch is B patches of h x w pixels, h <= H and w <= W.
+ * uz_patch_index (two launches, once per pool): index [M][P][H + 1] int32 (uz_patch_index_bytes), entry y of plane (m, p) the
+ *   number of foreground pixels in its rows 0..y-1, entry H the plane's total.  A wave counts a row by ballot + popcount over
+ *   64-pixel chunks, a second kernel scans the H counts of each plane: plain stores, no atomics, no memset.
+ * uz_patch_draw (one launch, one wavefront per patch): u (B, 8) fp32 uniforms in [0, 1) -> coords (B, 4) int32
+ *   [m, y0, x0, plane or -1].  pick(u, n) = min(n - 1, (int)floor((double)u * n)), one float64 product.
+ *   m = indices[b] with use_indices (a value outside 0..M-1: coords = [-1, 0, 0, -1], the patch is cut as zeros), else pick(u0, M).
+ *   Foreground mode, if u1 < pos (float32) and picture m has a non-empty plane: plane = the pick(u2, n_present)-th non-empty
+ *   plane in ascending order; (py, px) = its pick(u3, count)-th foreground pixel in row-major order (the row by a binary search
+ *   of the index, the column by a ballot / popcount walk of the row); the pixel lands at patch row
+ *   ry = min(h - 1, floor((0.5 + (u4 - 0.5) * jitter) * h)) in float64, every operation rounded (column: u5, w), so jitter 0
+ *   centres it and jitter 1 places it uniformly; y0 = clamp(py - ry, 0, H - h), x0 = clamp(px - rx, 0, W - w).
+ *   Random mode otherwise: y0 = pick(u4, H - h + 1), x0 = pick(u5, W - w + 1), plane = -1.  u6, u7 are reserved (not read).
+ *   A float32 uniform carries 24 bits: a plane with more than 2^24 foreground pixels is sampled on a 2^24-point lattice of
+ *   ranks (likewise a pool of more than 2^24 pictures or offsets).
+ * uz_patch_cut (one launch): image_out (B, C, h, w) fp32 and mask_out (B, Cm, h, w) fp32 or (B, h, w) int32, the window at
+ *   (y0, x0) of picture m.  fp32 pictures and both mask kinds are copied exactly; uint8 pictures become
+ *   fmaf((float)v, scale[c], shift[c]) with norm = [scale[0..C), shift[0..C)] fp32 on the device (NULL: scale 1, shift 0; fp32
+ *   pictures take no norm).  m outside 0..M-1 gives zeros; y0, x0 are clamped into the picture, nothing is read out of range.
+ *   A thread owns four consecutive pixels of one patch row for every plane: 16-byte stores when w % 4 == 0 and the outputs
+ *   are 16-byte aligned, 4-byte stores otherwise; loads are 4-byte / 1-byte (x0 is arbitrary).  uz_patch_cut_grid() returns the
+ *   number of workgroups and (units, nullable) the units they share out (a unit: 256 consecutive runs of four pixels of one
+ *   patch): units > workgroups means workgroups walk.
+ * UZ_EINVAL before any launch: null descriptor / pointer; a mask, index, indices or norm pointer that does not match
+ * mask_kind / use_indices / image_kind; M, H, W, B, h, w <= 0, C outside 1..4, Cm outside 1..8, P not Cm (fp32 mask), outside
+ * 1..8 (labels) or not 0 (no mask); h > H or w > W (pad upstream); pos or jitter outside [0, 1] or not finite; H W >= 2^30,
+ * M P (H + 1) >= 2^31, B max(C, Cm) h w >= 2^31; misaligned (4 bytes; uint8 pictures: none) or overlapping tensors. */
+#define UZ_PATCH_IMAGE_F32 0
+#define UZ_PATCH_IMAGE_U8 1
+#define UZ_PATCH_MASK_NONE 0
+#define UZ_PATCH_MASK_F32 1
+#define UZ_PATCH_MASK_I32 2
+typedef struct uz_patch_desc {
+  int M, C, H, W;
+  int image_kind;  /* UZ_PATCH_IMAGE_* */
+  int mask_kind;   /* UZ_PATCH_MASK_* */
+  int Cm;          /* channels of an fp32 mask */
+  int P;           /* foreground planes */
+  int B, h, w;     /* patches per batch and their size */
+  int use_indices; /* 1: the source pictures come from `indices` */
+  float pos;       /* probability of foreground mode */
+  float jitter;    /* 0: the chosen pixel at the patch centre .. 1: anywhere in the patch */
+} uz_patch_desc;
+long long uz_patch_index_bytes(const uz_patch_desc* d);
+int uz_patch_index(const uz_patch_desc* d, const void* mask, int* index, void* stream);
+int uz_patch_draw(const uz_patch_desc* d, const float* u, const int* indices /* nullable */, const int* index, const void* mask,
+                  int* coords, void* stream);
+int uz_patch_cut_grid(const uz_patch_desc* d, int* units /* nullable */);
+int uz_patch_cut(const uz_patch_desc* d, const void* image, const void* mask, const int* coords, const float* norm /* nullable */,
+                 float* image_out, void* mask_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Surface-distance metrics of a thresholded prediction A against its target B, per (image, class) pair, exact: Hausdorff,
  * percentile Hausdorff (HD95) and average symmetric surface distance as medpy's hd / hd95 / assd compute them in 2D with
  * connectivity 1.  uz_surface.hip

@@ -57,6 +57,7 @@ EXPORTS = (
     "uz_region_loss_workspace_bytes", "uz_region_loss",
     "uz_class_loss_workspace_bytes", "uz_class_loss",
     "uz_augment_params", "uz_augment_grid", "uz_augment_apply",
+    "uz_patch_index_bytes", "uz_patch_index", "uz_patch_draw", "uz_patch_cut_grid", "uz_patch_cut",
     "uz_surface_workspace_bytes", "uz_surface_grid", "uz_surface_metrics",
     "uz_boundary_workspace_bytes", "uz_boundary_grid", "uz_boundary_loss",
     "uz_lovasz_workspace_bytes", "uz_lovasz_grid", "uz_lovasz_loss",
@@ -192,6 +193,16 @@ class AugmentDesc(Structure):
         + [(n, c_float) for n in ("p_hflip", "p_vflip", "rotate", "scale_min", "scale_max", "translate", "brightness",
                                   "contrast", "image_fill", "mask_fill")] \
         + [("label_fill", c_int)]
+
+
+PATCH_IMAGE_F32, PATCH_IMAGE_U8 = 0, 1
+PATCH_MASK_NONE, PATCH_MASK_F32, PATCH_MASK_I32 = 0, 1, 2
+
+
+class PatchDesc(Structure):
+    """uz_patch_desc"""
+    _fields_ = [(n, c_int) for n in ("M", "C", "H", "W", "image_kind", "mask_kind", "Cm", "P", "B", "h", "w", "use_indices")] \
+        + [("pos", c_float), ("jitter", c_float)]
 
 
 SURFACE_BINARY, SURFACE_CLASS = 0, 1
@@ -451,6 +462,11 @@ def load():
     lib.uz_augment_params.argtypes = [POINTER(AugmentDesc), vp, vp, vp]
     lib.uz_augment_grid.argtypes = [POINTER(AugmentDesc), POINTER(c_int)]
     lib.uz_augment_apply.argtypes = [POINTER(AugmentDesc), vp, vp, vp, vp, vp, vp, vp]
+    lib.uz_patch_index_bytes.argtypes = [POINTER(PatchDesc)]
+    lib.uz_patch_index.argtypes = [POINTER(PatchDesc), vp, vp, vp]
+    lib.uz_patch_draw.argtypes = [POINTER(PatchDesc), vp, vp, vp, vp, vp, vp]
+    lib.uz_patch_cut_grid.argtypes = [POINTER(PatchDesc), POINTER(c_int)]
+    lib.uz_patch_cut.argtypes = [POINTER(PatchDesc), vp, vp, vp, vp, vp, vp, vp]
     lib.uz_surface_workspace_bytes.argtypes = [POINTER(SurfaceDesc)]
     lib.uz_surface_grid.argtypes = [POINTER(SurfaceDesc), POINTER(c_int)]
     lib.uz_surface_metrics.argtypes = [POINTER(SurfaceDesc), vp, vp, vp, vp, vp, vp]
@@ -473,7 +489,7 @@ def load():
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("uz_last_error_string", "uz_source_hash"):
-            fn.restype = ctypes.c_longlong if name.endswith("_workspace_bytes") else c_int
+            fn.restype = ctypes.c_longlong if name.endswith(("_workspace_bytes", "_index_bytes")) else c_int
     if lib.uz_abi_version() != 1:
         raise HipLibraryError("libunetzoo_hip.so ABI version mismatch; rebuild it")
     _lib = lib

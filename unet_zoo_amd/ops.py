@@ -1671,6 +1671,66 @@ def augment_apply(desc: "L.AugmentDesc", image: torch.Tensor, mask: Optional[tor
                                           image_out.data_ptr(), _p(mask_out), L.stream_ptr()), "uz_augment_apply")
 
 
+# ---- PatchSampler: foreground index of a device pool, patch coordinates from draws, the patches (uz_patch.hip) ----------------
+def patch_index_bytes(desc: "L.PatchDesc") -> int:
+    """bytes of the [M][P][H + 1] int32 foreground index of this pool (0 without a mask)"""
+    return L.check_count(L.load().uz_patch_index_bytes(byref(desc)), "uz_patch_index_bytes")
+
+
+def patch_index(desc: "L.PatchDesc", mask: torch.Tensor, index: torch.Tensor) -> None:
+    """index (M, P, H + 1) int32 <- per plane the exclusive prefix over rows of the per-row foreground count; two launches"""
+    L.require_cuda(mask, index)
+    assert mask.is_contiguous() and index.is_contiguous() and index.dtype == torch.int32
+    assert mask.dtype == (torch.float32 if desc.mask_kind == L.PATCH_MASK_F32 else torch.int32)
+    assert tuple(index.shape) == (desc.M, desc.P, desc.H + 1)
+    with _Timed("patch_index", 0.0, 4.0 * (mask.numel() * (1 if desc.mask_kind == L.PATCH_MASK_F32 else desc.P) + index.numel())):
+        L.check(L.load().uz_patch_index(byref(desc), mask.data_ptr(), index.data_ptr(), L.stream_ptr()), "uz_patch_index")
+
+
+def patch_draw(desc: "L.PatchDesc", u: torch.Tensor, indices: Optional[torch.Tensor], index: Optional[torch.Tensor],
+               mask: Optional[torch.Tensor], coords: torch.Tensor) -> None:
+    """coords (B, 4) int32 [m, y0, x0, plane or -1] <- u (B, 8) fp32 uniforms in [0, 1) (and indices (B,) int32 when the
+    descriptor says use_indices); one launch, one wavefront per patch"""
+    L.require_cuda(u, indices, index, mask, coords)
+    for t in (u, indices, index, mask, coords):
+        assert t is None or t.is_contiguous()
+    assert u.dtype == torch.float32 and tuple(u.shape) == (desc.B, 8)
+    assert coords.dtype == torch.int32 and tuple(coords.shape) == (desc.B, 4)
+    assert indices is None or (indices.dtype == torch.int32 and tuple(indices.shape) == (desc.B,))
+    assert index is None or (index.dtype == torch.int32 and tuple(index.shape) == (desc.M, desc.P, desc.H + 1))
+    with _Timed("patch_draw", 0.0, 48.0 * desc.B):
+        L.check(L.load().uz_patch_draw(byref(desc), u.data_ptr(), _p(indices), _p(index), _p(mask), coords.data_ptr(), L.stream_ptr()),
+                "uz_patch_draw")
+
+
+def patch_cut_grid(desc: "L.PatchDesc") -> tuple:
+    """(workgroups, units) of the uz_patch_cut launch for this descriptor: units > workgroups means workgroups walk"""
+    units = ctypes.c_int(0)
+    grid = L.check_count(L.load().uz_patch_cut_grid(byref(desc), byref(units)), "uz_patch_cut_grid")
+    return grid, units.value
+
+
+def patch_cut(desc: "L.PatchDesc", image: torch.Tensor, mask: Optional[torch.Tensor], coords: torch.Tensor,
+              norm: Optional[torch.Tensor], image_out: torch.Tensor, mask_out: Optional[torch.Tensor]) -> None:
+    """image_out (B, C, h, w) fp32 and mask_out <- the windows `coords` names of the pool image (M, C, H, W) fp32 / uint8 and
+    mask (fp32 (M, Cm, H, W) or int32 (M, H, W)); norm (2, C) fp32 = (scale, shift) for uint8 pictures; one launch"""
+    L.require_cuda(image, mask, coords, norm, image_out, mask_out)
+    for t in (image, mask, coords, norm, image_out, mask_out):
+        assert t is None or t.is_contiguous()
+    assert image.dtype == (torch.uint8 if desc.image_kind == L.PATCH_IMAGE_U8 else torch.float32)
+    assert tuple(image.shape) == (desc.M, desc.C, desc.H, desc.W) and tuple(image_out.shape) == (desc.B, desc.C, desc.h, desc.w)
+    assert image_out.dtype == torch.float32 and coords.dtype == torch.int32 and tuple(coords.shape) == (desc.B, 4)
+    assert norm is None or (norm.dtype == torch.float32 and norm.numel() == 2 * desc.C)
+    assert (mask is None) == (mask_out is None)
+    if mask is not None:
+        assert mask.dtype == mask_out.dtype and tuple(mask.shape) == (desc.M,) + tuple(mask.shape[1:-2]) + (desc.H, desc.W)
+        assert tuple(mask_out.shape) == (desc.B,) + tuple(mask.shape[1:-2]) + (desc.h, desc.w)
+    nb = 2.0 * 4 * (image_out.numel() + (mask_out.numel() if mask_out is not None else 0))
+    with _Timed("patch_cut", 0.0, nb):
+        L.check(L.load().uz_patch_cut(byref(desc), image.data_ptr(), _p(mask), coords.data_ptr(), _p(norm), image_out.data_ptr(),
+                                      _p(mask_out), L.stream_ptr()), "uz_patch_cut")
+
+
 # ---- SurfaceMetrics: Hausdorff / HD95 / ASSD of the thresholded maps (uz_surface.hip) ----------------------------------------
 def surface_grid(desc: "L.SurfaceDesc") -> tuple:
     """(workgroups, units) of the column pass of uz_surface_metrics for this descriptor: units > workgroups means workgroups

@@ -39,6 +39,13 @@ criterion route, phase 0 on the fused-loss route; the model and the criterion re
 (``step.augmented``).  Its draws are torch's generator's, so every replay draws afresh and a seed reproduces a run; with several
 ranks each rank draws from its OWN generator (seed the ranks differently unless they are meant to augment alike).  Without
 ``augment`` nothing changes: the same graphs, the same buffers, the same numbers.
+
+Patches from a device pool: ``GraphedStep(model, crit, source=unet_zoo_amd.PatchSampler(...))`` takes NO batch -- ``loss = step()``.
+The sampler's two launches (``uz_patch.hip``: draw the windows, cut them out) are captured at the head of the first graph, in
+front of the augmentation's when there is one, which then reads the sampler's static outputs as its raw batch; every replay
+draws its own patches (``step.sampled``, ``step.coords``) and the host does nothing per step.  The dry run that plans the graphs
+needs real patches, so ONE set of draws is consumed before the capture (with ``force_draws(u)`` that is not sticky, the forced
+ones).  With several ranks each rank holds its own pool and draws from its own generator.  Without ``source`` nothing changes.
 """
 from __future__ import annotations
 
@@ -50,6 +57,7 @@ import torch.nn as nn
 
 from .graph import PhasedStep
 from .augment import GpuAugment
+from .patches import PatchSampler
 from .capture import CAPTURE_MODE, _check_capture, _new_graph, _unwrap, resolve_criterion, static_copy, unchanged
 from .loss import MulticlassLoss, RegionLoss
 from .optim import FlatClipAdamW
@@ -57,8 +65,9 @@ from .optim import FlatClipAdamW
 
 class _ShapeGraphs:
     """everything captured for one (input shape, target shape): x / t take the caller's batch, mx / mt are what the model and
-    the criterion read -- the same tensors, or the static outputs of the augmentation `aug` captured in front of the model"""
-    __slots__ = ("x", "t", "mx", "mt", "aug", "fwd", "phases", "gouts", "loss", "dice", "outputs", "pool", "ps", "tables")
+    the criterion read -- the same tensors, or the static outputs of the augmentation `aug` captured in front of the model;
+    src: the patch sampler captured in front of both, whose static outputs are then x / t"""
+    __slots__ = ("x", "t", "mx", "mt", "aug", "src", "fwd", "phases", "gouts", "loss", "dice", "outputs", "pool", "ps", "tables")
 
 
 class GraphedStep:
@@ -66,9 +75,10 @@ class GraphedStep:
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-5,
                  max_norm: float = 1.0, phases: int = 5, process_group=None, data_parallel: Optional[bool] = None,
                  cu_reserve: Optional[int] = None, comm: str = "overlap", comm_dtype: Optional[torch.dtype] = None,
-                 augment: Optional[GpuAugment] = None):
+                 augment: Optional[GpuAugment] = None, source: Optional[PatchSampler] = None):
         """augment: a GpuAugment applied to every batch inside the first graph (module docstring); every rank draws from its own
         generator.
+        source: a PatchSampler whose patches ARE the batch: the step is then called without arguments (module docstring).
         comm: when the gradient exchange of a data-parallel step runs -- "overlap": the span of every finished backward
         phase is all-reduced while the next phase's graph runs; "tail": ONE all-reduce of the whole flat buffer after the
         last phase.  The same graphs serve both; autotune_comm() times them on the job's own hardware and keeps the faster
@@ -97,6 +107,14 @@ class GraphedStep:
         if augment is not None and not isinstance(augment, GpuAugment):
             raise TypeError(f"augment must be a unet_zoo_amd.GpuAugment, got {type(augment).__name__}")
         self.augment = augment
+        if source is not None and not isinstance(source, PatchSampler):
+            raise TypeError(f"source must be a unet_zoo_amd.PatchSampler, got {type(source).__name__}")
+        if source is not None and source.out_mask is None:
+            raise ValueError("source: the PatchSampler has no masks, a training step needs targets")
+        if source is not None and source.out_mask.dtype != self._target_dtype:
+            raise ValueError(f"source: the PatchSampler yields {source.out_mask.dtype} masks, the criterion takes {self._target_dtype} "
+                             "targets (class indices go with MulticlassLoss, fp32 masks with every other criterion)")
+        self.source = source
         self.lr, self.betas, self.eps, self.weight_decay, self.max_norm = lr, betas, eps, weight_decay, max_norm
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
@@ -189,11 +207,11 @@ class GraphedStep:
             torch.cuda.synchronize()
             self._capture_opt()
 
-    def _capture(self, x: torch.Tensor, t: torch.Tensor, aug=None) -> _ShapeGraphs:
+    def _capture(self, x: torch.Tensor, t: torch.Tensor, aug=None, src=None) -> _ShapeGraphs:
         """x, t: the static tensors the model and the criterion read; aug: the bound augmentation that writes them (its two
-        launches open the first graph) or None"""
+        launches open the first graph) or None; src: the bound patch sampler whose two launches come in front of those, or None"""
         g = _ShapeGraphs()
-        g.x, g.t, g.mx, g.mt, g.aug = x, t, x, t, aug
+        g.x, g.t, g.mx, g.mt, g.aug, g.src = x, t, x, t, aug, src
         ps = PhasedStep(self.model, self._loss_fn)
         cuts = self._cuts
         g.phases, g.fwd, g.gouts, g.dice, pool = [], None, None, None, None
@@ -218,6 +236,8 @@ class GraphedStep:
             # d(loss)/d(output) buffers
             g.fwd = _new_graph()
             with torch.cuda.graph(g.fwd, capture_error_mode=CAPTURE_MODE):
+                if src is not None:
+                    src.run()
                 if aug is not None:
                     aug.run()
                 ps.emit(g.mx)
@@ -230,6 +250,8 @@ class GraphedStep:
             gk = _new_graph()
             with torch.cuda.graph(gk, pool=pool, capture_error_mode=CAPTURE_MODE):
                 if k == 0 and self._fused_loss:
+                    if src is not None:
+                        src.run()
                     if aug is not None:
                         aug.run()
                     g.loss = ps.forward(g.mx, g.mt)
@@ -319,15 +341,31 @@ class GraphedStep:
         return None
 
     # ------------------------------------------------------------------ the step
-    def forward_backward(self, x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    def forward_backward(self, x: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None) -> torch.Tensor:
         """zero_grad + forward + loss + backward (+ gradient all-reduce): afterwards every ``p.grad`` (views of the flat
-        buffer) holds this step's (rank-averaged) gradient.  Returns the loss as a device scalar."""
-        key = (tuple(x.shape), tuple(target.shape))
+        buffer) holds this step's (rank-averaged) gradient.  Returns the loss as a device scalar.  With `source` the batch
+        is the sampler's and no argument is taken."""
+        if self.source is not None:
+            if x is not None or target is not None:
+                raise TypeError("this GraphedStep draws its batch from `source` (a PatchSampler): call it without arguments")
+            key = ("source",)
+        elif x is None or target is None:
+            raise TypeError("GraphedStep takes a batch (x, target); only a step built with source= is called without one")
+        else:
+            key = (tuple(x.shape), tuple(target.shape))
         g = self._graphs.get(key)
         if g is None:
-            # static input buffers of this shape (training_loop.py:109-110)
             dev = next(self.model.parameters()).device
-            sx, st = static_copy(x, dev), static_copy(target, dev, self._target_dtype)
+            src = None
+            if self.source is not None:
+                # the sampler's static outputs are the raw buffers; the dry run needs real patches: one set of draws is consumed
+                src = self.source.bind()
+                if src.out_image.device != dev:
+                    raise ValueError(f"source: the PatchSampler's pool is on {src.out_image.device}, the model on {dev}")
+                sx, st = src.run()
+            else:
+                # static input buffers of this shape (training_loop.py:109-110)
+                sx, st = static_copy(x, dev), static_copy(target, dev, self._target_dtype)
             aug, mx, mt = None, sx, st
             if self.augment is not None:
                 # the augmentation reads the raw copies and writes static outputs of its own; for the dry run they hold the
@@ -339,13 +377,14 @@ class GraphedStep:
                 mt.copy_(st)
             if self.opt is None:
                 self._setup(mx, mt)
-            g = self._graphs[key] = self._capture(mx, mt, aug)
+            g = self._graphs[key] = self._capture(mx, mt, aug, src)
             g.x, g.t = sx, st
         self._cur = g
-        if x.data_ptr() != g.x.data_ptr():
-            g.x.copy_(x)
-        if target.data_ptr() != g.t.data_ptr():
-            g.t.copy_(target)
+        if g.src is None:
+            if x.data_ptr() != g.x.data_ptr():
+                g.x.copy_(x)
+            if target.data_ptr() != g.t.data_ptr():
+                g.t.copy_(target)
         if g.fwd is not None:
             g.fwd.replay()
             loss = g.ps.loss(g.mt)                   # eager criterion; leaves d(loss)/d(output)
@@ -377,7 +416,7 @@ class GraphedStep:
                 gk.replay()
         return self.loss
 
-    def autotune_comm(self, x: torch.Tensor, target: torch.Tensor, steps: int = 6) -> Dict[str, float]:
+    def autotune_comm(self, x: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None, steps: int = 6) -> Dict[str, float]:
         """Time `steps` whole training steps under each collective schedule ("overlap", "tail") on this job's ranks and
         keep the faster one; every rank takes the same decision (the slowest rank's time counts).  These are real
         optimizer steps on (x, target).  Returns {"overlap": ms, "tail": ms}."""
@@ -410,7 +449,7 @@ class GraphedStep:
         self._g_opt.replay()
         self.steps_done += 1
 
-    def __call__(self, x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    def __call__(self, x: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None) -> torch.Tensor:
         loss = self.forward_backward(x, target)
         self.optimizer_step()
         return loss
@@ -428,6 +467,20 @@ class GraphedStep:
         return None if g is None or g.aug is None else (g.aug.out_image, g.aug.out_mask)
 
     @property
+    def sampled(self) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+        """(pictures, masks) the sampler cut for the last step, before any augmentation: its STATIC outputs (None without
+        `source`)"""
+        g = self._cur
+        return None if g is None or g.src is None else (g.src.out_image, g.src.out_mask)
+
+    @property
+    def coords(self) -> Optional[torch.Tensor]:
+        """(B, 4) int32 [picture, y0, x0, plane or -1] of the last step's patches: the sampler's STATIC tensor (None without
+        `source`)"""
+        g = self._cur
+        return None if g is None or g.src is None else g.src.coords
+
+    @property
     def flat_grad(self) -> torch.Tensor:
         return self.opt.flat_g[:self.opt.n]
 
@@ -436,8 +489,9 @@ class GraphedStep:
         k = len(self._cuts) - 1 if self._cuts else self.n_phases
         opt = "hipGraph(clip+AdamW on flat buffers, 3 launches)"
         crit = "" if self._fused_loss else "hipGraph(fwd) + eager criterion + "
-        if self.augment is not None:
-            crit = "GpuAugment at the head of the first hipGraph + " + crit
+        head = [name for name, opt_in in (("PatchSampler", self.source), ("GpuAugment", self.augment)) if opt_in is not None]
+        if head:
+            crit = " + ".join(head) + " at the head of the first hipGraph + " + crit
         if not self.distributed:
             return f"{crit}hipGraph({'fwd+' if self._fused_loss else ''}bwd) + {opt}"
         mb = [round((a1 - a0) * 4 / 2 ** 20, 1) for a0, a1 in self._spans]
