@@ -11,7 +11,6 @@ import boundary_ref as R  # tests/boundary_ref.py (pytest puts this directory on
 import unet_zoo_amd
 from unet_zoo_amd import BoundaryLoss, MulticlassLoss, RegionLoss
 from unet_zoo_amd import _lib as L
-from unet_zoo_amd.capture import resolve_criterion
 
 SHAPES = [(1, 1), (4, 4), (17, 23), (33, 20), (8, 150)]
 DENSITIES = [0.02, 0.3, 0.9]
@@ -140,12 +139,6 @@ def test_target_dtype_and_ignore_index_follow_the_base():
     assert BoundaryLoss(base=RegionLoss()).target_dtype == torch.float32 and not BoundaryLoss(base=RegionLoss()).class_mode
     c = BoundaryLoss(base=MulticlassLoss(ignore_index=255))
     assert c.target_dtype == torch.int32 and c.class_mode and c.ignore_index == 255
-
-
-def test_resolve_criterion_returns_a_fused_pair():
-    for c in (BoundaryLoss(), BoundaryLoss(base=MulticlassLoss())):
-        fused, dtype = resolve_criterion(c)
-        assert fused == (c.loss_and_dice, c.direct) and dtype == c.target_dtype
 
 
 def test_output_weights_are_the_bases():

@@ -11,7 +11,6 @@ import lovasz_ref as R  # tests/lovasz_ref.py (pytest puts this directory on sys
 import unet_zoo_amd
 from unet_zoo_amd import BoundaryLoss, LovaszLoss, MulticlassLoss, RegionLoss
 from unet_zoo_amd import _lib as L
-from unet_zoo_amd.capture import resolve_criterion
 
 
 # ---------------------------------------------------------------------------------------------------------- Berman's form
@@ -245,12 +244,6 @@ def test_target_dtype_ignore_index_and_weights_follow_the_base():
     maps = {"a": torch.zeros(1), "b": torch.zeros(1)}
     assert LovaszLoss().weights_for(maps) == (1.0, 1.0)
     assert LovaszLoss(base=RegionLoss(output_weights={"a": 1, "b": .5})).weights_for(maps) == (1.0, 0.5)
-
-
-def test_resolve_criterion_returns_a_fused_pair():
-    for c in (LovaszLoss(), LovaszLoss(base=MulticlassLoss())):
-        fused, dtype = resolve_criterion(c)
-        assert fused == (c.loss_and_dice, c.direct) and dtype == c.target_dtype
 
 
 def test_cpu_tensors_and_bad_shapes_are_refused_at_call():

@@ -10,7 +10,11 @@ order (name, flops, bytes of every timed launch; the 1x1 head, which has no timi
 sha256 of the outputs, the loss, every parameter gradient in named_parameters order and every module buffer after the step.
 Run it with the SAME kernel library in both source trees (UNET_ZOO_AMD_LIB); it uses only API that both trees have.
 `compare` prints one line per configuration and the first difference, exit status 1 on any; --log-only names configurations
-whose numbers differ between two records of ONE tree (compared on their launch log alone, and marked so in the output)."""
+whose numbers differ between two records of ONE tree (compared on their launch log alone, and marked so in the output).
+
+For a refactor of the criteria (criterion.py, loss.py, composed.py, boundary.py, lovasz.py) the criterion/ entries run every
+criterion eagerly in its three forms on every output container; there the log is the ordered list of torch operations a
+TorchDispatchMode sees around the call and its backward, with the library calls noted through their four entry points."""
 import hashlib
 import json
 import os
@@ -50,13 +54,13 @@ def _tensors(o):
     return [t for v in o for t in _tensors(v)]
 
 
-def _make(name, kw, dtype):
+def _make(name, kw, dtype, num_classes=1):
     torch.manual_seed(0)
     if name == "missformer":
         from unet_zoo_amd.models import MISSFormer
         m = MISSFormer(num_classes=1, in_channels=3, **kw)
     else:
-        m = unet_zoo_amd.create_model(name, in_channels=3, num_classes=1, **kw)
+        m = unet_zoo_amd.create_model(name, in_channels=3, num_classes=num_classes, **kw)
     m.run_dtype = dtype
     for mod in m.modules():          # dropout off: the records compare kernels, not generator states
         if isinstance(mod, torch.nn.Dropout):
@@ -103,6 +107,14 @@ def configs(nf):
                                                                switch={s: False})))
     out.append((f"switch/fuse_bn_finalize=True/unet/bf16/N{nf}", dict(model="unet", kw={}, b=nf, size=64, dtype="bf16", mode="train",
                                                                      switch={"fuse_bn_finalize": True})))
+    # the criteria (for a refactor of criterion.py / loss.py / composed.py / boundary.py / lovasz.py): eagerly in their three
+    # forms, then inside the graphs of the runners
+    for crit in CRITERIA:
+        out.append((f"criterion/{crit}", dict(mode="criterion", crit=crit)))
+    for crit in ("region", "multiclass", "boundary", "lovasz"):
+        for dt in ("bf16", "fp32"):
+            out.append((f"graphed_step/{crit}/unet/{dt}", dict(model="unet", kw={}, b=2, size=64, dtype=dt, mode="graphed_step", crit=crit)))
+    out.append(("graphed_eval/region/unet/bf16", dict(model="unet", kw={}, b=2, size=64, dtype="bf16", mode="graphed_eval", crit="region")))
     return out
 
 
@@ -157,12 +169,160 @@ def run_predict(cfg, m, x, sha):
     return _take_log()
 
 
+# ------------------------------------------------------------------------------------------------------------- the criteria
+CLASSES, IGNORE = 3, 255
+CRITERIA = (["bce_dice", "region", "tversky", "ce_dice"] + [f"boundary/{b}" for b in ("bce_dice", "region", "multiclass")]
+            + [f"lovasz/{b}/{p}" for b in ("bce_dice", "region", "multiclass") for p in ("per_image", "batch")])
+OUTPUT_WEIGHTS = {"tensor": (0.75,), "dict": {"d0": 1.0, "d1": 0.5, "d2": 0.25}, "list": (0.5, 1.0)}
+PUBLISHED = ("counts", "term", "sd2", "errors", "ranks")
+
+
+def _criterion(name, container="tensor"):
+    """(the criterion named in CRITERIA / by a graphed entry, whether its targets are class indices); "bce_dice" is a string"""
+    from unet_zoo_amd import BoundaryLoss, LovaszLoss, MulticlassLoss, RegionLoss
+    parts = name.split("/")
+    if parts[0] in ("boundary", "lovasz"):
+        base, cls = _criterion(parts[1] if len(parts) > 1 else "region")
+        if parts[0] == "boundary":
+            return BoundaryLoss(base=base, weight=0.05), cls
+        return LovaszLoss(base=base, weight=0.5, per_image=parts[-1] != "batch"), cls
+    if name == "bce_dice":
+        return "bce_dice", False
+    if name == "region":
+        return RegionLoss(), False
+    if name == "tversky":
+        return RegionLoss.tversky(0.6, 0.4, gamma=1.5, reduce="channel", output_weights=OUTPUT_WEIGHTS[container]), False
+    if name in ("ce_dice", "multiclass"):
+        return MulticlassLoss.ce_dice(class_weight=(0.5, 1.0, 2.0), ignore_index=IGNORE), True
+    raise SystemExit(f"no criterion {name!r}")
+
+
+def _labels(b, h, w, seed):
+    """class indices with ignored pixels and ONE value outside [0, CLASSES)"""
+    g = torch.Generator().manual_seed(seed)
+    y = torch.randint(0, CLASSES, (b, h, w), generator=g)
+    y[torch.rand(b, h, w, generator=g) < 0.1] = IGNORE
+    y[0, 1, 2] = CLASSES + 4
+    return y
+
+
+def _op_log(log):
+    """a mode under which every torch operation is noted in `log`, in order"""
+    from torch.utils._python_dispatch import TorchDispatchMode
+
+    class OpLog(TorchDispatchMode):
+        def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+            log.append([str(func), None, None])
+            return func(*args, **(kwargs or {}))
+    return OpLog()
+
+
+def _note_library_calls(log):
+    """the four entry points every criterion's kernels are called through, noted in `log` with the number of maps and which of
+    them take a gradient; returns what undoes it"""
+    from unet_zoo_amd import _lib as L
+    saved = [(L, "region_loss"), (L, "class_loss"), (ops, "boundary_loss"), (ops, "lovasz_loss")]
+    saved = [(mod, n, getattr(mod, n)) for mod, n in saved]
+
+    def wrap(n, real):
+        def call(desc, items, *a):
+            log.append(["library:" + n, len(items), "".join("0" if it.dlogits is None else "1" for it in items)])
+            return real(desc, items, *a)
+        return call
+    for mod, n, real in saved:
+        setattr(mod, n, wrap(n, real))
+
+    def undo():
+        for mod, n, real in saved:
+            setattr(mod, n, real)
+    return undo
+
+
+def run_criterion(cfg, sha):
+    """one criterion eagerly: loss_and_dice (+ backward), __call__ (+ backward) and direct, on a tensor, a dict of three and a
+    list of two, fp32 and bf16 logits; once with a map that needs no gradient and once under no_grad (on tensors that ask for no
+    gradient, as GraphedEval hands them over)"""
+    from unet_zoo_amd.loss import loss_and_dice, loss_and_dice_direct
+    log = []
+    undo = _note_library_calls(log)
+    cases = [(c, dt, form, "") for c in ("tensor", "dict", "list") for dt in ("fp32", "bf16") for form in ("loss_and_dice", "call", "direct")]
+    cases += [("dict", "fp32", "loss_and_dice", "one_map_without_gradient"), ("dict", "bf16", "loss_and_dice", "no_grad")]
+    crits = {}
+    try:
+        for container, dt, form, special in cases:
+            if container not in crits:          # (output weights by key go with dict outputs only)
+                crits[container] = _criterion(cfg["crit"], container)
+            crit, cls = crits[container]
+            C = CLASSES if cls else 2
+            g = torch.Generator().manual_seed(11)
+            n = {"tensor": 1, "dict": 3, "list": 2}[container]
+            maps = [(2.0 * torch.randn(2, C, 24, 20, generator=g)).to(torch.bfloat16 if dt == "bf16" else torch.float32).cuda() for _ in range(n)]
+            t = _labels(2, 24, 20, 12).cuda() if cls else (torch.rand(2, C, 24, 20, generator=g) > 0.6).float().cuda()
+            if special != "no_grad":
+                for i, v in enumerate(maps):
+                    v.requires_grad_(not (special and i == 1))
+            outs = maps[0] if container == "tensor" else ({f"d{i}": v for i, v in enumerate(maps)} if container == "dict" else list(maps))
+            tag = "/".join(x for x in (container, dt, form, special) if x)
+            log.append(["# " + tag, None, None])
+            lad = loss_and_dice if crit == "bce_dice" else crit.loss_and_dice
+            with _op_log(log):
+                if form == "direct":
+                    loss, dice, grads = (loss_and_dice_direct if crit == "bce_dice" else crit.direct)(outs, t)
+                elif special == "no_grad":
+                    with torch.no_grad():
+                        loss, dice = lad(outs, t)
+                    grads = ()
+                else:
+                    if form == "call":
+                        loss, dice = (lad(outs, t)[0] if crit == "bce_dice" else crit(outs, t)), None
+                    else:
+                        loss, dice = lad(outs, t)
+                    log.append(["# backward", None, None])
+                    loss.backward()
+                    grads = [v.grad for v in maps]
+            torch.cuda.synchronize()
+            sha[tag + "/loss"] = _sha(loss)
+            sha[tag + "/dice"] = _sha(dice) if dice is not None else "none"
+            for i, gr in enumerate(grads):
+                sha[f"{tag}/grad{i}"] = f"{gr.dtype} {_sha(gr)}" if gr is not None else "none"
+            for obj, pre in ((crit, ""), (getattr(crit, "base", None), "base.")):
+                for name in PUBLISHED:
+                    v = getattr(obj, name, None)
+                    if isinstance(v, torch.Tensor):
+                        sha[f"{tag}/{pre}{name}"] = _sha(v)
+    finally:
+        undo()
+    return log
+
+
+def backward_seen(log):
+    """does the log of a criterion entry hold the multiplication (d * g_loss) of every backward?"""
+    backwards = hits = 0
+    inside = hit = False
+    for name, _, _ in log + [["# end", None, None]]:
+        if name.startswith("# "):
+            hits += inside and hit
+            inside, hit = name == "# backward", False
+            backwards += inside
+        elif inside and name.startswith("aten.mul"):
+            hit = True
+    return hits == backwards
+
+
 def run_step(cfg, m, x, t, sha):
-    """GraphedStep: two steps; loss, dice and outputs after each, every parameter and buffer after the second"""
+    """GraphedStep: two steps (a composed criterion: a third after set_weights); loss, dice and outputs after each, every
+    parameter and buffer after the last"""
     import torch.nn.functional as F
-    crit = "bce_dice" if cfg["crit"] == "bce_dice" else (lambda o, tt: F.binary_cross_entropy_with_logits(o, tt))
+    if cfg["crit"] == "callable":
+        crit = lambda o, tt: F.binary_cross_entropy_with_logits(o, tt)      # noqa: E731
+    else:
+        crit = _criterion(cfg["crit"])[0]
     step = unet_zoo_amd.GraphedStep(m.train(), crit, lr=1e-2)
-    for tag in ("first", "second"):
+    for tag in ("first", "second", "reweighted"):
+        if tag == "reweighted":
+            if not hasattr(crit, "set_weights"):
+                break
+            crit.set_weights(weight=0.25, base_scale=0.5)
         step(x, t)
         _results(sha, tag, step, ("loss", "dice", "outputs"))
     for n, p in m.named_parameters():
@@ -173,16 +333,21 @@ def run_step(cfg, m, x, t, sha):
 
 def run(cfg):
     from unet_zoo_amd.loss import loss_and_dice
-    dtype = torch.bfloat16 if cfg["dtype"] == "bf16" else torch.float32
-    m = _make(cfg["model"], cfg["kw"], dtype)
-    x, t = _batch(cfg["b"], cfg["size"])
     sha = {}
+    if cfg["mode"] == "criterion":
+        return run_criterion(cfg, sha), sha
+    dtype = torch.bfloat16 if cfg["dtype"] == "bf16" else torch.float32
+    labels = cfg.get("crit") == "multiclass"
+    m = _make(cfg["model"], cfg["kw"], dtype, CLASSES if labels else 1)
+    x, t = _batch(cfg["b"], cfg["size"])
+    if labels:
+        t = _labels(cfg["b"], cfg["size"], cfg["size"], 3).cuda()
     torch.manual_seed(2)
     if cfg["mode"] in ("graphed_predict", "tiled", "graphed_step"):
         log = run_predict(cfg, m, x, sha) if cfg["mode"] != "graphed_step" else run_step(cfg, m, x, t, sha)
         outs = []
     elif cfg["mode"] == "graphed_eval":
-        ev = unet_zoo_amd.GraphedEval(m.eval(), "bce_dice", fold_bn=True)
+        ev = unet_zoo_amd.GraphedEval(m.eval(), _criterion(cfg.get("crit", "bce_dice"))[0], fold_bn=True)
         ops.profile_begin()
         ev._forward(x)                  # the launches of the captured forward, eagerly (a capture takes no timing events)
         log = _take_log()
@@ -275,6 +440,10 @@ def compare(pa, pb, log_only):
     a, b = json.load(open(pa)), json.load(open(pb))
     bad = 0
     print(f"batch of the folded entries: N = {a['folds_batch']}")
+    seen = [backward_seen(c["log"]) for r in (a, b) for c in r["configs"] if c["name"].startswith("criterion/")]
+    if seen:
+        print("criterion entries: the log is the torch operations and library calls; the backward's mul is "
+              + ("in every log" if all(seen) else "NOT in the log (the gradients' sha256 cover the backward)"))
     if a["folds_batch"] != b["folds_batch"] or [c["name"] for c in a["configs"]] != [c["name"] for c in b["configs"]]:
         print("the two records hold different configurations")
         return 1

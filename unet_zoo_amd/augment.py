@@ -26,8 +26,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-
-_INT_DTYPES = (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64)
+from .criterion import INT_DTYPES
 
 
 class _Bound:
@@ -177,7 +176,7 @@ class GpuAugment:
         return b
 
     def __call__(self, images: torch.Tensor, masks: Optional[torch.Tensor] = None):
-        if masks is not None and isinstance(masks, torch.Tensor) and masks.dtype in _INT_DTYPES and masks.dtype != torch.int32:
+        if masks is not None and isinstance(masks, torch.Tensor) and masks.dtype in INT_DTYPES and masks.dtype != torch.int32:
             masks = masks.to(torch.int32)
         key = (tuple(images.shape), None if masks is None else (tuple(masks.shape), masks.dtype), images.device) \
             if isinstance(images, torch.Tensor) else None

@@ -85,31 +85,26 @@ class BoundaryLoss(ComposedLoss):
             raise ValueError(f"BoundaryLoss: alpha must be in [0, 1], got {alpha!r}")
         self.set_weights(weight=a, base_scale=1.0 - a)
 
-    def _plan(self, n_items: int, shape, device: torch.device, main: int):
-        key = (n_items, tuple(shape), device.index, main)
-        plan = self._plans.get(key)
-        if plan is None:
-            if n_items > L.CLASS_MAX_ITEMS:
-                raise ValueError(f"BoundaryLoss: {n_items} output maps, at most {L.CLASS_MAX_ITEMS} per call")
-            N, C, H, W = (int(s) for s in shape)
-            if self.class_mode and not 2 <= C <= L.CLASS_MAX_K:
-                raise ValueError(f"BoundaryLoss: K = {C} classes outside [2, {L.CLASS_MAX_K}]")
-            if H > _MAX_HW or W > _MAX_HW:
-                raise ValueError(f"BoundaryLoss: maps of {H} x {W} pixels, at most {_MAX_HW} a side")
-            first = 0 if (self.include_background or not self.class_mode) else 1
-            desc = L.BoundaryDesc(L.BOUNDARY_CLASS if self.class_mode else L.BOUNDARY_BINARY, n_items, N, C, H, W, first,
-                                  self.ignore_index, main, self.spacing)
-            ws = torch.empty((L.boundary_workspace_bytes(desc) + 7) // 8, dtype=torch.float64, device=device)
-            sd2 = torch.zeros(N * (C - first), H, W, dtype=torch.int32, device=device)
-            plan = self._plans[key] = (desc, (L.BoundaryItem * n_items)(), ws, sd2)
-        return plan
+    def _build_plan(self, n_items: int, shape, device: torch.device, main: int):
+        if n_items > L.CLASS_MAX_ITEMS:
+            raise ValueError(f"BoundaryLoss: {n_items} output maps, at most {L.CLASS_MAX_ITEMS} per call")
+        N, C, H, W = (int(s) for s in shape)
+        if self.class_mode and not 2 <= C <= L.CLASS_MAX_K:
+            raise ValueError(f"BoundaryLoss: K = {C} classes outside [2, {L.CLASS_MAX_K}]")
+        if H > _MAX_HW or W > _MAX_HW:
+            raise ValueError(f"BoundaryLoss: maps of {H} x {W} pixels, at most {_MAX_HW} a side")
+        first = 0 if (self.include_background or not self.class_mode) else 1
+        desc = L.BoundaryDesc(L.BOUNDARY_CLASS if self.class_mode else L.BOUNDARY_BINARY, n_items, N, C, H, W, first,
+                              self.ignore_index, main, self.spacing)
+        ws = torch.empty((L.boundary_workspace_bytes(desc) + 7) // 8, dtype=torch.float64, device=device)
+        sd2 = torch.zeros(N * (C - first), H, W, dtype=torch.int32, device=device)
+        return desc, (L.BoundaryItem * n_items)(), ws, sd2
 
     def _term(self, xs, t: torch.Tensor, shape, dl, weights, main: int, base_loss: torch.Tensor) -> torch.Tensor:
         """one uz_boundary_loss over all maps on the gradients the base wrote"""
         desc, items, ws, sd2 = self._plan(len(xs), shape, t.device, main)
         out = torch.empty(2, dtype=torch.float32, device=t.device)
-        for it, x, d, w in zip(items, xs, dl, weights):
-            it.logits, it.dlogits, it.weight = x.data_ptr(), (d.data_ptr() if d is not None else None), w
+        self._fill(items, xs, dl, weights)
         ops.boundary_loss(desc, items, t, self._scales_on(t.device), base_loss, out, sd2, ws)
         self.sd2, self.term = sd2, out[1]
         return out[0]

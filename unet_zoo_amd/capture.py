@@ -22,9 +22,8 @@ import torch.nn as nn
 from . import _lib as L
 from .engine import Engine
 from .graph import HipModule
-from .boundary import BoundaryLoss
-from .loss import MulticlassLoss, RegionLoss, loss_and_dice, loss_and_dice_direct
-from .lovasz import LovaszLoss
+from .criterion import FusedCriterion
+from .loss import loss_and_dice, loss_and_dice_direct
 
 # hipGraph capture checks only THIS thread's calls: the process-group watchdog thread polls its events concurrently
 # (legal for it, but fatal to a capture in the default "global" mode)
@@ -109,17 +108,16 @@ def unchanged(module: nn.Module, device: torch.device):
 
 def resolve_criterion(criterion) -> Tuple[Optional[Tuple[Callable, Callable]], torch.dtype]:
     """(fused, target_dtype) of a runner's ``criterion`` argument.  fused: the (autograd, direct) forms of a loss that sits
-    INSIDE the graphs -- "bce_dice" (loss.py's fused kernel) or a RegionLoss / MulticlassLoss instance (uz_region_loss /
-    uz_class_loss: deterministic, no library reduction, graph-safe, they hand over their own gradients) -- or None for any other
-    callable, which is evaluated EAGERLY outside the graphs: library reductions must not be captured on this stack
-    (DESIGN.md 5a).  target_dtype: the static target buffer's -- float32 masks, or what the criterion asks for
-    (MulticlassLoss: int32 class indices)."""
+    INSIDE the graphs -- "bce_dice" (loss.py's fused kernel) or a FusedCriterion (criterion.py: deterministic, no library
+    reduction, graph-safe, it hands over its own gradients) -- or None for any other callable, which is evaluated EAGERLY
+    outside the graphs: library reductions must not be captured on this stack.  target_dtype: the static target
+    buffer's -- float32 masks, or what the criterion asks for (MulticlassLoss: int32 class indices)."""
     target_dtype = getattr(criterion, "target_dtype", torch.float32)
     if isinstance(criterion, str):
         if criterion != "bce_dice":
             raise ValueError(f"unknown built-in criterion {criterion!r}; pass 'bce_dice' or a callable")
         return (loss_and_dice, loss_and_dice_direct), target_dtype
-    if isinstance(criterion, (RegionLoss, MulticlassLoss, BoundaryLoss, LovaszLoss)):
+    if isinstance(criterion, FusedCriterion):
         return (criterion.loss_and_dice, criterion.direct), target_dtype
     return None, target_dtype
 

@@ -1,44 +1,28 @@
 """What the criteria composed on a base loss share (``BoundaryLoss``: boundary.py, ``LovaszLoss``: lovasz.py): ``loss =
 base_scale * base + weight * term`` with the base's launch first and ONE launch sequence of the term's kernels on the gradients
 the base wrote; ``weight`` and ``base_scale`` in two device scalars that the kernels read, so that ``set_weights`` reaches a
-captured graph without a new capture; one autograd node for all output maps; the ``direct`` form of the graphed step.
+captured graph without a new capture.  The three forms are ``FusedCriterion``'s (criterion.py).
 
-A subclass sets ``_NAME`` (the prefix of its messages) and implements ``_term``.
+A subclass sets ``_NAME`` (the prefix of its messages) and implements ``_build_plan`` and ``_term``.
 """
 from __future__ import annotations
 
-import math
 from typing import Optional, Tuple
 
 import torch
 
 from . import _lib as L
-from .loss import MulticlassLoss, RegionLoss, _INT_DTYPES, _maps_of, bce_dice_direct, bce_dice_with_logits
+from .criterion import INT_DTYPES, FusedCriterion, maps_of
+from .loss import MulticlassLoss, RegionLoss, bce_dice_direct, bce_dice_with_logits
 
 
-class _ComposedFn(torch.autograd.Function):
-    """ONE node for all output maps: forward is the base's launch plus the term's launches on the gradients it wrote"""
-
-    @staticmethod
-    def forward(ctx, crit: "ComposedLoss", target: torch.Tensor, weights: tuple, main: int, *logits: torch.Tensor):
-        loss, dice, dl = crit._launch(logits, target, weights, main, ctx.needs_input_grad[4:])
-        ctx.dl = dl
-        ctx.in_dtypes = tuple(v.dtype for v in logits)
-        ctx.mark_non_differentiable(dice)
-        return loss, dice
-
-    @staticmethod
-    def backward(ctx, g_loss, _g_dice):
-        return (None, None, None, None) + tuple(None if d is None else (d * g_loss).to(dt)
-                                                for d, dt in zip(ctx.dl, ctx.in_dtypes))
-
-
-class ComposedLoss:
-    """``base_scale * base + weight * term``: the settings, the base's launch and the three forms of a composed criterion"""
+class ComposedLoss(FusedCriterion):
+    """``base_scale * base + weight * term``: the settings and the base's launch of a composed criterion"""
 
     _NAME = "ComposedLoss"
 
     def __init__(self, base, weight, base_scale):
+        super().__init__()     # _plans: what the term keeps per (number of maps, logits shape, device index, main)
         name = self._NAME
         if isinstance(base, str):
             if base != "bce_dice":
@@ -49,21 +33,10 @@ class ComposedLoss:
         self.class_mode = isinstance(base, MulticlassLoss)
         self.weight, self.base_scale = self._check_weights(weight, base_scale)
         self.ignore_index = base.ignore_index if self.class_mode else -100
-        self._plans = {}       # (number of maps, logits shape, device index, main) -> what the term keeps for that shape
-        self._scales = {}      # device index -> (weight, base_scale) on the device: what the kernels (and the graphs) read
+        self._scales = {}     # device index -> (weight, base_scale) on the device: what the kernels (and the graphs) read
         self.term: Optional[torch.Tensor] = None
 
     # ------------------------------------------------------------------ the settings
-    @classmethod
-    def _num(cls, name, v) -> float:
-        try:
-            f = float(v)
-        except (TypeError, ValueError):
-            raise ValueError(f"{cls._NAME}: {name} must be a number, got {v!r}") from None
-        if not math.isfinite(f):
-            raise ValueError(f"{cls._NAME}: {name} must be finite, got {v!r}")
-        return f
-
     @classmethod
     def _check_weights(cls, weight, base_scale) -> Tuple[float, float]:
         w, b = cls._num("weight", weight), cls._num("base_scale", base_scale)
@@ -96,7 +69,7 @@ class ComposedLoss:
     def weights_for(self, outputs) -> tuple:
         """the weight of every output map, in the order the model emits them: the base's"""
         if isinstance(self.base, str):
-            return (1.0,) * len(_maps_of(outputs)[1])
+            return (1.0,) * len(maps_of(outputs)[1])
         return self.base.weights_for(outputs)
 
     # ------------------------------------------------------------------ the launches
@@ -136,7 +109,7 @@ class ComposedLoss:
             if v.dtype not in (torch.float32, torch.bfloat16):
                 raise ValueError(f"{name}: logits must be float32 or bfloat16, got {v.dtype}")
         if self.class_mode:
-            if target.dtype not in _INT_DTYPES:
+            if target.dtype not in INT_DTYPES:
                 raise ValueError(f"{name}: the target holds class indices and must have an integer dtype, got {target.dtype}")
             want = (shape[0],) + shape[2:]
             if tuple(target.shape) not in (want, (shape[0], 1) + shape[2:]):
@@ -158,20 +131,3 @@ class ComposedLoss:
             t = target.detach().contiguous().float()
         loss = self._term(xs, t, shape, dl, weights, main, base_loss.detach().reshape(1))
         return loss, dice, dl
-
-    # ------------------------------------------------------------------ the three forms
-    def loss_and_dice(self, outputs, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(loss, the base's Dice metric of the main output) as 0-dim device tensors; the loss is differentiable with respect
-        to every output tensor through ONE autograd node; under ``no_grad`` no gradient buffer is touched"""
-        _, maps, main = _maps_of(outputs)
-        return _ComposedFn.apply(self, target, self.weights_for(outputs), main, *maps)
-
-    def __call__(self, outputs, target: torch.Tensor) -> torch.Tensor:
-        return self.loss_and_dice(outputs, target)[0]
-
-    def direct(self, outputs, target: torch.Tensor):
-        """(loss, dice, d(loss)/d(outputs)) without an autograd node -- the graphed step's form: the base's launch, then the
-        term's on the gradients it returned (fp32, in the order the model emits its outputs)"""
-        _, maps, main = _maps_of(outputs)
-        loss, dice, dl = self._launch(maps, target, self.weights_for(outputs), main, (True,) * len(maps))
-        return loss, dice, tuple(dl)

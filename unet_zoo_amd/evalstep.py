@@ -42,7 +42,8 @@ import torch
 import torch.nn as nn
 
 from .capture import GraphedRunner, resolve_criterion, static_copy
-from .loss import MulticlassLoss, RegionLoss, loss_and_dice
+from .criterion import FusedCriterion
+from .loss import loss_and_dice
 from .surface import SurfaceMetrics
 
 
@@ -54,7 +55,7 @@ class _EvalGraph:
 class GraphedEval(GraphedRunner):
     PASS = "the EVALUATION pass"
 
-    def __init__(self, model: nn.Module, criterion: Union[str, RegionLoss, MulticlassLoss, Callable] = "bce_dice", *, fold_bn: bool = False,
+    def __init__(self, model: nn.Module, criterion: Union[str, FusedCriterion, Callable] = "bce_dice", *, fold_bn: bool = False,
                  surface: Optional[SurfaceMetrics] = None):
         super().__init__(model, fold_bn)
         if surface is not None and not isinstance(surface, SurfaceMetrics):
@@ -68,6 +69,7 @@ class GraphedEval(GraphedRunner):
         fused, self._target_dtype = resolve_criterion(criterion)
         self._fused_loss = fused is not None
         self._fused = fused[0] if self._fused_loss else None
+        self._per_shape_state = isinstance(criterion, FusedCriterion)
         self._loss_fn = None if self._fused_loss else criterion
         self.loss: Optional[torch.Tensor] = None
         self.dice: Optional[torch.Tensor] = None
@@ -82,8 +84,8 @@ class GraphedEval(GraphedRunner):
 
         def warm():
             out = self._forward(x)
-            if self._fused_loss and self._fused is not loss_and_dice:
-                with torch.no_grad():      # a RegionLoss / MulticlassLoss keeps its workspace (counts, class weights) per shape:
+            if self._per_shape_state:
+                with torch.no_grad():      # a FusedCriterion keeps its workspace (counts, class weights) per shape:
                     # allocated here, outside the capture
                     self._fused(out, t)
             if self._surface is not None:      # its workspace, out and stats of this shape: allocated outside the capture too
@@ -92,7 +94,7 @@ class GraphedEval(GraphedRunner):
         def pipeline():
             g.outputs = self._forward(g.x)
             if self._fused_loss:
-                with torch.no_grad():      # no gradient: uz_bce_dice / uz_region_loss / uz_class_loss run with dlogits = NULL
+                with torch.no_grad():      # no gradient: the criterion's kernels run with dlogits = NULL
                     g.loss, g.dice = self._fused(g.outputs, g.t)
             g.surface = self._surface(g.outputs, g.t) if self._surface is not None else None
 

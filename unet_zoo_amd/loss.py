@@ -12,25 +12,30 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib as L
+from .criterion import INT_DTYPES, FusedCriterion, maps_of
+
+
+def _bce_dice_launch(logits: torch.Tensor, target: torch.Tensor, need_grad: bool):
+    """one uz_bce_dice pass -> ((loss, dice) as one fp32 tensor of two, d(loss)/d(logits) in fp32 or None)"""
+    L.require_cuda(logits, target)
+    assert logits.shape == target.shape, (logits.shape, target.shape)
+    x = logits.detach().contiguous().float()
+    t = target.detach().contiguous().float()
+    n = x.numel()
+    lib = L.load()
+    dlogits = torch.empty_like(x) if need_grad else None
+    out = torch.empty(2, dtype=torch.float32, device=x.device)
+    ws = torch.empty(L.check_count(lib.uz_bce_dice_workspace_bytes(n), "uz_bce_dice_workspace_bytes") // 8,
+                     dtype=torch.float64, device=x.device)
+    L.check(lib.uz_bce_dice(x.data_ptr(), t.data_ptr(), n, dlogits.data_ptr() if need_grad else None, out.data_ptr(),
+                            ws.data_ptr(), L.stream_ptr()), "uz_bce_dice")
+    return out, dlogits
 
 
 class _BceDice(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits: torch.Tensor, target: torch.Tensor):
-        L.require_cuda(logits, target)
-        assert logits.shape == target.shape, (logits.shape, target.shape)
-        x = logits.detach().contiguous().float()
-        t = target.detach().contiguous().float()
-        n = x.numel()
-        lib = L.load()
-        need_grad = ctx.needs_input_grad[0]
-        dlogits = torch.empty_like(x) if need_grad else None
-        out = torch.empty(2, dtype=torch.float32, device=x.device)
-        ws = torch.empty(L.check_count(lib.uz_bce_dice_workspace_bytes(n), "uz_bce_dice_workspace_bytes") // 8,
-                         dtype=torch.float64, device=x.device)
-        L.check(lib.uz_bce_dice(x.data_ptr(), t.data_ptr(), n, dlogits.data_ptr() if need_grad else None, out.data_ptr(),
-                                ws.data_ptr(), L.stream_ptr()), "uz_bce_dice")
-        ctx.dlogits = dlogits
+        out, ctx.dlogits = _bce_dice_launch(logits, target, ctx.needs_input_grad[0])
         ctx.in_dtype = logits.dtype
         dice = out[1]
         ctx.mark_non_differentiable(dice)
@@ -44,18 +49,7 @@ class _BceDice(torch.autograd.Function):
 def bce_dice_direct(logits: torch.Tensor, target: torch.Tensor):
     """(loss, dice, d(loss)/d(logits)) from ONE kernel pass and nothing else: no autograd node, hence none of the launches
     loss.backward() adds (the ones_like fill, the multiplication by it, a cast) -- the graphed step's form"""
-    L.require_cuda(logits, target)
-    assert logits.shape == target.shape, (logits.shape, target.shape)
-    x = logits.detach().contiguous().float()
-    t = target.detach().contiguous().float()
-    n = x.numel()
-    lib = L.load()
-    dlogits = torch.empty_like(x)
-    out = torch.empty(2, dtype=torch.float32, device=x.device)
-    ws = torch.empty(L.check_count(lib.uz_bce_dice_workspace_bytes(n), "uz_bce_dice_workspace_bytes") // 8,
-                     dtype=torch.float64, device=x.device)
-    L.check(lib.uz_bce_dice(x.data_ptr(), t.data_ptr(), n, dlogits.data_ptr(), out.data_ptr(), ws.data_ptr(),
-                            L.stream_ptr()), "uz_bce_dice")
+    out, dlogits = _bce_dice_launch(logits, target, True)
     return out[0], out[1], dlogits
 
 
@@ -64,12 +58,10 @@ def loss_and_dice_direct(outputs, target: torch.Tensor):
     them (HipModule.wrap_outputs keeps that order for dicts and lists); the summed losses of u2net's seven maps /
     nested_unet's deep-supervision heads have unit weights (training_loop.py:24-32, 60-64), so each map's gradient is its
     own BCE gradient"""
-    if isinstance(outputs, dict):
-        trip = [bce_dice_direct(v, target) for v in outputs.values()]
-        return sum(p[0] for p in trip), trip[0][1], tuple(p[2] for p in trip)
-    if isinstance(outputs, (list, tuple)):
-        trip = [bce_dice_direct(v, target) for v in outputs]
-        return sum(p[0] for p in trip), trip[-1][1], tuple(p[2] for p in trip)
+    if isinstance(outputs, (dict, list, tuple)):
+        _, maps, main = maps_of(outputs)
+        trip = [bce_dice_direct(v, target) for v in maps]
+        return sum(p[0] for p in trip), trip[main][1], tuple(p[2] for p in trip)
     l, d, g = bce_dice_direct(outputs, target)
     return l, d, (g,)
 
@@ -83,12 +75,10 @@ def loss_and_dice(outputs, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Te
     """The step's loss and main-output Dice for every output container of the zoo: a tensor; u2net's dict
     (sum over d0..d6, Dice of d0; training_loop.py:24-32); nested_unet's deep-supervision list (sum, Dice of the
     last = finest output)."""
-    if isinstance(outputs, dict):
-        pairs = [bce_dice_with_logits(v, target) for v in outputs.values()]
-        return sum(p[0] for p in pairs), pairs[0][1]
-    if isinstance(outputs, (list, tuple)):
-        pairs = [bce_dice_with_logits(v, target) for v in outputs]
-        return sum(p[0] for p in pairs), pairs[-1][1]
+    if isinstance(outputs, (dict, list, tuple)):
+        _, maps, main = maps_of(outputs)
+        pairs = [bce_dice_with_logits(v, target) for v in maps]
+        return sum(p[0] for p in pairs), pairs[main][1]
     return bce_dice_with_logits(outputs, target)
 
 
@@ -98,34 +88,7 @@ def loss_and_dice(outputs, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Te
 _REDUCES = ("batch", "image", "channel")
 
 
-def _maps_of(outputs):
-    """(keys or None, the output tensors in the order the model emits them, index of the main output): first value of a
-    dict, last element of a list -- as loss_and_dice picks the map of the Dice metric"""
-    if isinstance(outputs, dict):
-        return tuple(outputs.keys()), tuple(outputs.values()), 0
-    if isinstance(outputs, (list, tuple)):
-        return None, tuple(outputs), len(outputs) - 1
-    return None, (outputs,), 0
-
-
-class _RegionFn(torch.autograd.Function):
-    """ONE node for all output maps: forward is one uz_region_loss call that also writes every map's gradient"""
-
-    @staticmethod
-    def forward(ctx, crit: "RegionLoss", target: torch.Tensor, weights: tuple, main: int, *logits: torch.Tensor):
-        loss, dice, dl = crit._launch(logits, target, weights, main, ctx.needs_input_grad[4:])
-        ctx.dl = dl
-        ctx.in_dtypes = tuple(v.dtype for v in logits)
-        ctx.mark_non_differentiable(dice)
-        return loss, dice
-
-    @staticmethod
-    def backward(ctx, g_loss, _g_dice):
-        return (None, None, None, None) + tuple(None if d is None else (d * g_loss).to(dt)
-                                                for d, dt in zip(ctx.dl, ctx.in_dtypes))
-
-
-class RegionLoss:
+class RegionLoss(FusedCriterion):
     """``w_bce * BCEWithLogits + w_region * region`` on the device, for every output container of the zoo.
 
     Per output map (logits ``x`` and target ``t`` of one shape ``(N, K, H, W)``; ``p = sigmoid(x)``)::
@@ -156,16 +119,12 @@ class RegionLoss:
     be ordered by the caller (``GraphedStep`` / ``GraphedEval`` and plain training loops are).
     """
 
+    _NAME = "RegionLoss"
+
     def __init__(self, w_bce: float = 1.0, w_region: float = 1.0, alpha: float = 0.5, beta: float = 0.5,
                  smooth: float = 1.0, gamma: float = 1.0, reduce: str = "image", pos_weight=None, output_weights=None):
-        def num(name, v):
-            try:
-                f = float(v)
-            except (TypeError, ValueError):
-                raise ValueError(f"RegionLoss: {name} must be a number, got {v!r}") from None
-            if f != f or f in (float("inf"), float("-inf")):
-                raise ValueError(f"RegionLoss: {name} must be finite, got {v!r}")
-            return f
+        super().__init__()       # _plans: (descriptor, item table, workspace) per key
+        num = self._num
         self.w_bce, self.w_region = num("w_bce", w_bce), num("w_region", w_region)
         self.alpha, self.beta = num("alpha", alpha), num("beta", beta)
         self.smooth, self.gamma = num("smooth", smooth), num("gamma", gamma)
@@ -185,17 +144,7 @@ class RegionLoss:
         if reduce not in _REDUCES:
             raise ValueError(f"RegionLoss: reduce must be one of {_REDUCES}, got {reduce!r}")
         self.reduce = reduce
-        if output_weights is None:
-            self.output_weights = None
-        elif isinstance(output_weights, dict):
-            self.output_weights = {k: num(f"output_weights[{k!r}]", v) for k, v in output_weights.items()}
-        else:
-            self.output_weights = tuple(num(f"output_weights[{i}]", v) for i, v in enumerate(output_weights))
-        if self.output_weights is not None:
-            vals = self.output_weights.values() if isinstance(self.output_weights, dict) else self.output_weights
-            if any(v < 0 for v in vals):
-                raise ValueError(f"RegionLoss: output_weights must be >= 0, got {output_weights!r}")
-        self._plans = {}     # (number of maps, shape, device index) -> (descriptor, item table, workspace)
+        self.output_weights = self._output_weights(output_weights)
 
     @classmethod
     def dice(cls, smooth: float = 1.0, **kw) -> "RegionLoss":
@@ -207,24 +156,6 @@ class RegionLoss:
         """BCE + Tversky loss (``gamma > 1``: focal Tversky); alpha weighs false positives, beta false negatives"""
         return cls(alpha=alpha, beta=beta, **kw)
 
-    # ------------------------------------------------------------------ the containers
-    def weights_for(self, outputs) -> tuple:
-        """the weight of every output map, in the order the model emits them"""
-        keys, maps, _ = _maps_of(outputs)
-        ow = self.output_weights
-        if ow is None:
-            return (1.0,) * len(maps)
-        if isinstance(ow, dict):
-            if keys is None:
-                raise ValueError("RegionLoss: output_weights is a dict but the outputs are not")
-            missing = [k for k in keys if k not in ow]
-            if missing:
-                raise ValueError(f"RegionLoss: output_weights has no entry for the outputs {missing}")
-            return tuple(ow[k] for k in keys)
-        if len(ow) != len(maps):
-            raise ValueError(f"RegionLoss: {len(ow)} output_weights for {len(maps)} output maps")
-        return ow
-
     def _groups(self, shape) -> int:
         if self.reduce == "batch":
             return 1
@@ -232,20 +163,16 @@ class RegionLoss:
             raise ValueError(f"RegionLoss: reduce={self.reduce!r} needs (N, K, ...) maps, got shape {tuple(shape)}")
         return int(shape[0]) if self.reduce == "image" else int(shape[0]) * int(shape[1])
 
-    def _plan(self, n_items: int, shape, device: torch.device, main: int):
-        key = (n_items, tuple(shape), device.index, main)
-        plan = self._plans.get(key)
-        if plan is None:
-            if n_items > L.REGION_MAX_ITEMS:
-                raise ValueError(f"RegionLoss: {n_items} output maps, at most {L.REGION_MAX_ITEMS} per call")
-            n = 1
-            for s in shape:
-                n *= int(s)
-            desc = L.RegionDesc(n_items, n, self._groups(shape), self.w_bce, self.w_region, self.alpha, self.beta,
-                                self.smooth, self.gamma, self.pos_weight, main)
-            ws = torch.empty((L.region_loss_workspace_bytes(desc) + 7) // 8, dtype=torch.float64, device=device)
-            plan = self._plans[key] = (desc, (L.RegionItem * n_items)(), ws)
-        return plan
+    def _build_plan(self, n_items: int, shape, device: torch.device, main: int):
+        if n_items > L.REGION_MAX_ITEMS:
+            raise ValueError(f"RegionLoss: {n_items} output maps, at most {L.REGION_MAX_ITEMS} per call")
+        n = 1
+        for s in shape:
+            n *= int(s)
+        desc = L.RegionDesc(n_items, n, self._groups(shape), self.w_bce, self.w_region, self.alpha, self.beta,
+                            self.smooth, self.gamma, self.pos_weight, main)
+        ws = torch.empty((L.region_loss_workspace_bytes(desc) + 7) // 8, dtype=torch.float64, device=device)
+        return desc, (L.RegionItem * n_items)(), ws
 
     def _launch(self, logits, target: torch.Tensor, weights, main: int, need):
         """one uz_region_loss over all maps -> (loss, dice, [d(loss)/d(map) in fp32, or None where need is False])"""
@@ -265,27 +192,11 @@ class RegionLoss:
         desc, items, ws = self._plan(len(xs), t.shape, t.device, main)
         dl = [torch.empty_like(x) if g else None for x, g in zip(xs, need)]
         out = torch.empty(2, dtype=torch.float32, device=t.device)
-        for it, x, d, w in zip(items, xs, dl, weights):
-            it.logits, it.target, it.dlogits, it.weight = x.data_ptr(), t.data_ptr(), (d.data_ptr() if d is not None else None), w
+        self._fill(items, xs, dl, weights)
+        for it in items:           # (an item of this kernel names its target too: all maps share one)
+            it.target = t.data_ptr()
         L.region_loss(desc, items, out, ws)
         return out[0], out[1], dl
-
-    # ------------------------------------------------------------------ the three forms
-    def loss_and_dice(self, outputs, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(loss, Dice metric of the main output) as 0-dim device tensors; the loss is differentiable with respect to every
-        output tensor through ONE autograd node (any CUDA fp32 / bf16 logits: a stock torch model's too)"""
-        _, maps, main = _maps_of(outputs)
-        return _RegionFn.apply(self, target, self.weights_for(outputs), main, *maps)
-
-    def __call__(self, outputs, target: torch.Tensor) -> torch.Tensor:
-        return self.loss_and_dice(outputs, target)[0]
-
-    def direct(self, outputs, target: torch.Tensor):
-        """(loss, dice, d(loss)/d(outputs)) without an autograd node -- the graphed step's form; the gradients (fp32) come in
-        the order the model emits its outputs (HipModule.wrap_outputs keeps it), as from loss_and_dice_direct"""
-        _, maps, main = _maps_of(outputs)
-        loss, dice, dl = self._launch(maps, target, self.weights_for(outputs), main, (True,) * len(maps))
-        return loss, dice, tuple(dl)
 
     def __repr__(self) -> str:
         return (f"RegionLoss(w_bce={self.w_bce}, w_region={self.w_region}, alpha={self.alpha}, beta={self.beta}, "
@@ -297,27 +208,9 @@ class RegionLoss:
 # Softmax cross-entropy + soft Dice over class-index labels: uz_class_loss, three launches for any number of output maps
 # ---------------------------------------------------------------------------------------------------------------------
 _CLASS_REDUCES = {"batch": L.CLASS_REDUCE_BATCH, "image": L.CLASS_REDUCE_IMAGE}
-_INT_DTYPES = (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64)
 
 
-class _MulticlassFn(torch.autograd.Function):
-    """ONE node for all output maps: forward is one uz_class_loss call that also writes every map's gradient"""
-
-    @staticmethod
-    def forward(ctx, crit: "MulticlassLoss", target: torch.Tensor, weights: tuple, main: int, *logits: torch.Tensor):
-        loss, dice, dl = crit._launch(logits, target, weights, main, ctx.needs_input_grad[4:])
-        ctx.dl = dl
-        ctx.in_dtypes = tuple(v.dtype for v in logits)
-        ctx.mark_non_differentiable(dice)
-        return loss, dice
-
-    @staticmethod
-    def backward(ctx, g_loss, _g_dice):
-        return (None, None, None, None) + tuple(None if d is None else (d * g_loss).to(dt)
-                                                for d, dt in zip(ctx.dl, ctx.in_dtypes))
-
-
-class MulticlassLoss:
+class MulticlassLoss(FusedCriterion):
     """``w_ce * CrossEntropy + w_dice * Dice`` over softmax probabilities on the device, for every output container of the zoo.
 
     Per output map (logits ``x`` of shape ``(N, K, H, W)``, labels ``y`` of shape ``(N, H, W)`` or ``(N, 1, H, W)`` holding
@@ -359,19 +252,14 @@ class MulticlassLoss:
     ``RegionLoss`` does.
     """
 
+    _NAME = "MulticlassLoss"
     target_dtype = torch.int32
 
     def __init__(self, w_ce: float = 1.0, w_dice: float = 1.0, smooth: float = 1.0, label_smoothing: float = 0.0,
                  class_weight=None, ignore_index: int = -100, include_background: bool = True, reduce: str = "image",
                  square: bool = False, output_weights=None):
-        def num(name, v):
-            try:
-                f = float(v)
-            except (TypeError, ValueError):
-                raise ValueError(f"MulticlassLoss: {name} must be a number, got {v!r}") from None
-            if f != f or f in (float("inf"), float("-inf")):
-                raise ValueError(f"MulticlassLoss: {name} must be finite, got {v!r}")
-            return f
+        super().__init__()       # _plans: (descriptor, item table, workspace, counts) per key
+        num = self._num
         self.w_ce, self.w_dice = num("w_ce", w_ce), num("w_dice", w_dice)
         self.smooth, self.label_smoothing = num("smooth", smooth), num("label_smoothing", label_smoothing)
         if self.w_ce < 0 or self.w_dice < 0:
@@ -398,18 +286,8 @@ class MulticlassLoss:
                 raise ValueError(f"MulticlassLoss: class_weight must have 2 .. {L.CLASS_MAX_K} entries, got {len(self.class_weight)}")
             if any(v < 0 for v in self.class_weight):
                 raise ValueError(f"MulticlassLoss: class_weight must be >= 0, got {class_weight!r}")
-        if output_weights is None:
-            self.output_weights = None
-        elif isinstance(output_weights, dict):
-            self.output_weights = {k: num(f"output_weights[{k!r}]", v) for k, v in output_weights.items()}
-        else:
-            self.output_weights = tuple(num(f"output_weights[{i}]", v) for i, v in enumerate(output_weights))
-        if self.output_weights is not None:
-            vals = self.output_weights.values() if isinstance(self.output_weights, dict) else self.output_weights
-            if any(v < 0 for v in vals):
-                raise ValueError(f"MulticlassLoss: output_weights must be >= 0, got {output_weights!r}")
-        self._plans = {}       # (number of maps, logits shape, device index, main) -> (descriptor, item table, workspace, counts)
-        self._cw_dev = {}      # device index -> the class weights, uploaded once
+        self.output_weights = self._output_weights(output_weights)
+        self._cw_dev = {}     # device index -> the class weights, uploaded once
         self.counts: Optional[torch.Tensor] = None
 
     @classmethod
@@ -421,38 +299,16 @@ class MulticlassLoss:
         kw.setdefault("reduce", "batch")
         return cls(w_ce=w_ce, w_dice=w_dice, **kw)
 
-    # ------------------------------------------------------------------ the containers
-    def weights_for(self, outputs) -> tuple:
-        """the weight of every output map, in the order the model emits them"""
-        keys, maps, _ = _maps_of(outputs)
-        ow = self.output_weights
-        if ow is None:
-            return (1.0,) * len(maps)
-        if isinstance(ow, dict):
-            if keys is None:
-                raise ValueError("MulticlassLoss: output_weights is a dict but the outputs are not")
-            missing = [k for k in keys if k not in ow]
-            if missing:
-                raise ValueError(f"MulticlassLoss: output_weights has no entry for the outputs {missing}")
-            return tuple(ow[k] for k in keys)
-        if len(ow) != len(maps):
-            raise ValueError(f"MulticlassLoss: {len(ow)} output_weights for {len(maps)} output maps")
-        return ow
-
-    def _plan(self, n_items: int, shape, device: torch.device, main: int):
-        key = (n_items, tuple(shape), device.index, main)
-        plan = self._plans.get(key)
-        if plan is None:
-            N, K = int(shape[0]), int(shape[1])
-            hw = 1
-            for s in shape[2:]:
-                hw *= int(s)
-            desc = L.ClassDesc(n_items, N, K, hw, self.w_ce, self.w_dice, self.smooth, self.label_smoothing, self.ignore_index,
-                               _CLASS_REDUCES[self.reduce], int(self.include_background), int(self.square), main)
-            ws = torch.empty((L.class_loss_workspace_bytes(desc) + 7) // 8, dtype=torch.float64, device=device)
-            counts = torch.zeros(K + 1, 3, dtype=torch.int64, device=device)
-            plan = self._plans[key] = (desc, (L.ClassItem * n_items)(), ws, counts)
-        return plan
+    def _build_plan(self, n_items: int, shape, device: torch.device, main: int):
+        N, K = int(shape[0]), int(shape[1])
+        hw = 1
+        for s in shape[2:]:
+            hw *= int(s)
+        desc = L.ClassDesc(n_items, N, K, hw, self.w_ce, self.w_dice, self.smooth, self.label_smoothing, self.ignore_index,
+                           _CLASS_REDUCES[self.reduce], int(self.include_background), int(self.square), main)
+        ws = torch.empty((L.class_loss_workspace_bytes(desc) + 7) // 8, dtype=torch.float64, device=device)
+        counts = torch.zeros(K + 1, 3, dtype=torch.int64, device=device)
+        return desc, (L.ClassItem * n_items)(), ws, counts
 
     def _weights_on(self, device: torch.device, K: int):
         if self.class_weight is None:
@@ -470,7 +326,7 @@ class MulticlassLoss:
             raise ValueError("MulticlassLoss: no output map")
         if len(logits) > L.CLASS_MAX_ITEMS:
             raise ValueError(f"MulticlassLoss: {len(logits)} output maps, at most {L.CLASS_MAX_ITEMS} per call")
-        if target.dtype not in _INT_DTYPES:
+        if target.dtype not in INT_DTYPES:
             raise ValueError(f"MulticlassLoss: the target holds class indices and must have an integer dtype, got {target.dtype}")
         shape = tuple(logits[0].shape)
         if len(shape) < 3:
@@ -502,28 +358,10 @@ class MulticlassLoss:
         desc, items, ws, counts = self._plan(len(xs), shape, y.device, main)
         dl = [torch.empty_like(x) if g else None for x, g in zip(xs, need)]
         out = torch.empty(2, dtype=torch.float32, device=y.device)
-        for it, x, d, w in zip(items, xs, dl, weights):
-            it.logits, it.dlogits, it.weight = x.data_ptr(), (d.data_ptr() if d is not None else None), w
+        self._fill(items, xs, dl, weights)
         L.class_loss(desc, items, y, cw, out, counts, ws)
         self.counts = counts
         return out[0], out[1], dl
-
-    # ------------------------------------------------------------------ the three forms
-    def loss_and_dice(self, outputs, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(loss, Dice metric of the main output) as 0-dim device tensors; the loss is differentiable with respect to every
-        output tensor through ONE autograd node (any CUDA fp32 / bf16 logits: a stock torch model's too)"""
-        _, maps, main = _maps_of(outputs)
-        return _MulticlassFn.apply(self, target, self.weights_for(outputs), main, *maps)
-
-    def __call__(self, outputs, target: torch.Tensor) -> torch.Tensor:
-        return self.loss_and_dice(outputs, target)[0]
-
-    def direct(self, outputs, target: torch.Tensor):
-        """(loss, dice, d(loss)/d(outputs)) without an autograd node -- the graphed step's form; the gradients (fp32) come in
-        the order the model emits its outputs"""
-        _, maps, main = _maps_of(outputs)
-        loss, dice, dl = self._launch(maps, target, self.weights_for(outputs), main, (True,) * len(maps))
-        return loss, dice, tuple(dl)
 
     def __repr__(self) -> str:
         return (f"MulticlassLoss(w_ce={self.w_ce}, w_dice={self.w_dice}, smooth={self.smooth}, "

@@ -78,34 +78,29 @@ class LovaszLoss(ComposedLoss):
         self.errors: Optional[torch.Tensor] = None   # _plans holds (descriptor, item table, workspace, errors, ranks) per key
         self.ranks: Optional[torch.Tensor] = None
 
-    def _plan(self, n_items: int, shape, device: torch.device, main: int):
-        key = (n_items, tuple(shape), device.index, main)
-        plan = self._plans.get(key)
-        if plan is None:
-            if n_items > L.CLASS_MAX_ITEMS:
-                raise ValueError(f"LovaszLoss: {n_items} output maps, at most {L.CLASS_MAX_ITEMS} per call")
-            N, C, H, W = (int(s) for s in shape)
-            if self.class_mode and not 2 <= C <= L.CLASS_MAX_K:
-                raise ValueError(f"LovaszLoss: K = {C} classes outside [2, {L.CLASS_MAX_K}]")
-            seg = (N * C, H * W) if self.per_image else (C, N * H * W)
-            if seg[1] > L.LOVASZ_MAX_SEGMENT:
-                raise ValueError(f"LovaszLoss: a segment of {seg[1]} elements, at most {L.LOVASZ_MAX_SEGMENT}")
-            if n_items * N * C * H * W > L.LOVASZ_MAX_ELEMENTS:
-                raise ValueError(f"LovaszLoss: {n_items * N * C * H * W} elements in {n_items} maps, at most {L.LOVASZ_MAX_ELEMENTS}")
-            desc = L.LovaszDesc(L.LOVASZ_CLASS if self.class_mode else L.LOVASZ_BINARY, n_items, N, C, H, W, int(self.per_image),
-                                L.LOVASZ_ALL if self.classes == "all" else L.LOVASZ_PRESENT, self.ignore_index, main)
-            ws = torch.empty((L.lovasz_workspace_bytes(desc) + 7) // 8, dtype=torch.float64, device=device)
-            errors = torch.zeros(seg, dtype=torch.float32, device=device)
-            ranks = torch.full(seg, -1, dtype=torch.int32, device=device)
-            plan = self._plans[key] = (desc, (L.LovaszItem * n_items)(), ws, errors, ranks)
-        return plan
+    def _build_plan(self, n_items: int, shape, device: torch.device, main: int):
+        if n_items > L.CLASS_MAX_ITEMS:
+            raise ValueError(f"LovaszLoss: {n_items} output maps, at most {L.CLASS_MAX_ITEMS} per call")
+        N, C, H, W = (int(s) for s in shape)
+        if self.class_mode and not 2 <= C <= L.CLASS_MAX_K:
+            raise ValueError(f"LovaszLoss: K = {C} classes outside [2, {L.CLASS_MAX_K}]")
+        seg = (N * C, H * W) if self.per_image else (C, N * H * W)
+        if seg[1] > L.LOVASZ_MAX_SEGMENT:
+            raise ValueError(f"LovaszLoss: a segment of {seg[1]} elements, at most {L.LOVASZ_MAX_SEGMENT}")
+        if n_items * N * C * H * W > L.LOVASZ_MAX_ELEMENTS:
+            raise ValueError(f"LovaszLoss: {n_items * N * C * H * W} elements in {n_items} maps, at most {L.LOVASZ_MAX_ELEMENTS}")
+        desc = L.LovaszDesc(L.LOVASZ_CLASS if self.class_mode else L.LOVASZ_BINARY, n_items, N, C, H, W, int(self.per_image),
+                            L.LOVASZ_ALL if self.classes == "all" else L.LOVASZ_PRESENT, self.ignore_index, main)
+        ws = torch.empty((L.lovasz_workspace_bytes(desc) + 7) // 8, dtype=torch.float64, device=device)
+        errors = torch.zeros(seg, dtype=torch.float32, device=device)
+        ranks = torch.full(seg, -1, dtype=torch.int32, device=device)
+        return desc, (L.LovaszItem * n_items)(), ws, errors, ranks
 
     def _term(self, xs, t: torch.Tensor, shape, dl, weights, main: int, base_loss: torch.Tensor) -> torch.Tensor:
         """one uz_lovasz_loss over all maps on the gradients the base wrote"""
         desc, items, ws, errors, ranks = self._plan(len(xs), shape, t.device, main)
         out = torch.empty(2, dtype=torch.float32, device=t.device)
-        for it, x, d, w in zip(items, xs, dl, weights):
-            it.logits, it.dlogits, it.weight = x.data_ptr(), (d.data_ptr() if d is not None else None), w
+        self._fill(items, xs, dl, weights)
         ops.lovasz_loss(desc, items, t, self._scales_on(t.device), base_loss, out, errors, ranks, ws)
         self.errors, self.ranks, self.term = errors, ranks, out[1]
         return out[0]

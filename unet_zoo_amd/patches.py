@@ -28,9 +28,8 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .criterion import INT_DTYPES
 from .data import IMAGENET_MEAN, IMAGENET_STD
-
-_INT_DTYPES = (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64)
 
 
 class PatchSampler:
@@ -82,7 +81,7 @@ class PatchSampler:
                     raise ValueError("PatchSampler: num_classes goes with integer masks (class indices) only")
                 kind, Cm = L.PATCH_MASK_F32, masks.shape[1]
                 P = Cm
-            elif masks.dtype in _INT_DTYPES:
+            elif masks.dtype in INT_DTYPES:
                 if tuple(masks.shape) != (M, H, W):
                     raise ValueError(f"PatchSampler: integer masks (class indices) must be (M, H, W) = ({M}, {H}, {W}) to go with "
                                      f"images {tuple(images.shape)}, got {tuple(masks.shape)}")
@@ -148,7 +147,7 @@ class PatchSampler:
                                ("itself" if want else "from set_indices()") + "; choose before the first captured call")
         if indices is not None:
             idx = torch.as_tensor(indices)
-            if idx.dtype not in _INT_DTYPES or tuple(idx.shape) != (self.batch,):
+            if idx.dtype not in INT_DTYPES or tuple(idx.shape) != (self.batch,):
                 raise ValueError(f"PatchSampler.set_indices: {self.batch} integer indices (one per patch), got "
                                  f"{idx.dtype} {tuple(idx.shape)}")
             self.indices.copy_(idx.to(device=self.device, dtype=torch.int32))

@@ -34,7 +34,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .loss import _maps_of
+from .criterion import maps_of
 
 _MODES = {"binary": L.POST_BINARY, "class": L.POST_CLASS}
 
@@ -106,7 +106,7 @@ class MaskPostprocess:
 
     # ------------------------------------------------------------------ one call
     def __call__(self, outputs_or_prob, *, mode: str = "auto", from_logits: bool = True) -> torch.Tensor:
-        _, maps, main = _maps_of(outputs_or_prob)
+        _, maps, main = maps_of(outputs_or_prob)
         x = maps[main]
         if not isinstance(x, torch.Tensor):
             raise ValueError("MaskPostprocess: the input must be a tensor (or a dict / list of output tensors)")

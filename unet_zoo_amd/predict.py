@@ -36,7 +36,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from .capture import GraphedRunner, static_copy
-from .loss import _maps_of
+from .criterion import maps_of
 from .postprocess import MaskPostprocess, resolve_mode
 
 
@@ -125,7 +125,7 @@ class GraphedPredict(Predictor):
         g.outputs = outs[0]
         mains = []
         for o in outs:
-            _, maps, main = _maps_of(o)
+            _, maps, main = maps_of(o)
             mains.append(maps[main].contiguous())
         shape = tuple(mains[0].shape)
         if len(shape) != 4:

@@ -24,11 +24,11 @@ BASELINE configs[1]).  ``GraphedStep`` is the same step captured once and replay
 them in place, so read (``.item()``) or ``.clone()`` what must outlive the step.
 
 Loss: the default ``criterion="bce_dice"`` is the fused kernel of ``loss.py`` (BCEWithLogits + its gradient + the
-Dice metric, one pass) inside the first graph.  A ``loss.RegionLoss`` instance (BCE + soft Dice / Tversky / focal Tversky,
-weighted over the output maps) sits in the same place: three launches inside the first graph, ``step.dice`` keeps its
-meaning; with several ranks each rank evaluates it on its own shard, so ``reduce="batch"`` is per shard.  A
-``loss.MulticlassLoss`` instance (softmax cross-entropy + Dice over class-index labels) sits there too; the static target
-buffer is then int32 (the criterion's ``target_dtype``), float32 for every other criterion.  Any other
+Dice metric, one pass) inside the first graph.  Any ``criterion.FusedCriterion`` (``RegionLoss``: BCE + soft Dice / Tversky /
+focal Tversky, weighted over the output maps; ``MulticlassLoss``: softmax cross-entropy + Dice over class-index labels; the
+criteria composed on them) sits in the same place: its launches inside the first graph, ``step.dice`` keeps its meaning;
+with several ranks each rank evaluates it on its own shard, so ``reduce="batch"`` is per shard.  The static target
+buffer has the criterion's ``target_dtype``: int32 for class-index labels, float32 for every other criterion.  Any other
 callable ``criterion(outputs, target) -> loss`` works too; it is evaluated EAGERLY between the forward graph and the
 backward graphs, because library reductions must not be captured on this stack: a memset node of a replayed hipGraph writes its value only in the first replay, and torch's multi-block
 reductions reset their semaphores with exactly such a node (tools/graph_canary.py).
@@ -59,7 +59,7 @@ from .graph import PhasedStep
 from .augment import GpuAugment
 from .patches import PatchSampler
 from .capture import CAPTURE_MODE, _check_capture, _new_graph, _unwrap, resolve_criterion, static_copy, unchanged
-from .loss import MulticlassLoss, RegionLoss
+from .criterion import FusedCriterion
 from .optim import FlatClipAdamW
 
 
@@ -71,7 +71,7 @@ class _ShapeGraphs:
 
 
 class GraphedStep:
-    def __init__(self, model: nn.Module, criterion: Union[str, RegionLoss, MulticlassLoss, Callable] = "bce_dice", *, lr: float = 1e-4,
+    def __init__(self, model: nn.Module, criterion: Union[str, FusedCriterion, Callable] = "bce_dice", *, lr: float = 1e-4,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-5,
                  max_norm: float = 1.0, phases: int = 5, process_group=None, data_parallel: Optional[bool] = None,
                  cu_reserve: Optional[int] = None, comm: str = "overlap", comm_dtype: Optional[torch.dtype] = None,

@@ -29,7 +29,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .loss import _INT_DTYPES, _maps_of
+from .criterion import INT_DTYPES, maps_of
 
 
 class SurfaceMetrics:
@@ -90,7 +90,7 @@ class SurfaceMetrics:
 
     # ------------------------------------------------------------------ one call
     def __call__(self, outputs, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        _, maps, main = _maps_of(outputs)
+        _, maps, main = maps_of(outputs)
         x = maps[main]
         if not isinstance(x, torch.Tensor) or not isinstance(target, torch.Tensor):
             raise ValueError("SurfaceMetrics: outputs and target must be tensors (or a dict / list of output tensors)")
@@ -103,7 +103,7 @@ class SurfaceMetrics:
             raise ValueError("SurfaceMetrics: empty maps")
         if shape[2] > L.SURFACE_MAX_HW or shape[3] > L.SURFACE_MAX_HW:
             raise ValueError(f"SurfaceMetrics: maps of {shape[2]} x {shape[3]} pixels, at most {L.SURFACE_MAX_HW} each way")
-        if target.dtype in _INT_DTYPES:
+        if target.dtype in INT_DTYPES:
             mode = L.SURFACE_CLASS
             K = shape[1]
             if not 2 <= K <= L.CLASS_MAX_K:

@@ -41,7 +41,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from .capture import static_copy
-from .loss import _maps_of
+from .criterion import maps_of
 from .postprocess import MaskPostprocess, resolve_mode
 from .predict import Predictor
 
@@ -116,7 +116,7 @@ class SlidingWindowPredict(Predictor):
                 ops.flip_views(views[0], self.views & ~1, views[1:])
             mains = []
             for v in views:
-                _, maps, main = _maps_of(self._forward(v))
+                _, maps, main = maps_of(self._forward(v))
                 mains.append(maps[main].contiguous())
             shape = tuple(mains[0].shape)
             if len(shape) != 4 or shape[0] != tn or shape[2:] != self.window:
