@@ -674,6 +674,50 @@ int uz_clip_adamw(float* p, const float* g, float* m, float* v, long long n, flo
                   void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The scheduled step tail: the arithmetic of uz_clip_adamw with the learning rate, the step counter and the EMA decay
+ * held on the device, an optional averaged copy of the weights and an optional accumulated gradient.  uz_steptail.hip
+ * Three launches: per-workgroup float64 sums of squares of the effective gradient; one workgroup that forms the norm, the
+ * clip coefficient, t + 1, the bias corrections, the rate and the EMA decay into `state`; one streaming pass over p, g, (acc),
+ * m, v, (ema).  With sched = UZ_SCHED_CONSTANT, warmup_steps = 0 and acc = ema = NULL, p, m and v come out bit-identical to
+ * uz_clip_adamw's for the rate state[1].
+ * Effective gradient: g when acc is NULL, else (g + acc) * (1.f / accumulate), the mean of `accumulate` micro-batch gradients
+ *   of which acc holds the sum of all but the last (uz_tail_accumulate).  The norm, the clipping and AdamW all see this mean.
+ * Schedule, closed-form in t = state[0] BEFORE the call (the 0-based index of the step being taken), evaluated in double and
+ *   rounded once to float; L = state[1], W = warmup_steps, T = total_steps, u = clamp((t - W) / (T - W), 0, 1):
+ *     t < W (every form)  lr = L * (warmup_start + (1 - warmup_start) * t / W)
+ *     UZ_SCHED_CONSTANT   lr = L
+ *     UZ_SCHED_COSINE     lr = min_lr + (L - min_lr) * 0.5 * (1 + cos(pi * u))
+ *     UZ_SCHED_POLY       lr = min_lr + (L - min_lr) * (1 - u)^power
+ *     UZ_SCHED_STEP       lr = max(min_lr, L * gamma^floor((t - W) / every))
+ * EMA (ema != NULL), after the AdamW update of an element: e += (1 - d) * (p_new - e), d = ema_decay, or with ema_warmup
+ *   d = min(ema_decay, (1 + t) / (10 + t)).
+ * state: 8 device floats.  [0] optimizer steps done (advanced by the call); [1] the base rate, written by the host (the call
+ *   only reads it); the call writes [2] the rate it used, [3] the EMA decay it used (0 without ema), [4] the clip
+ *   coefficient, [5] the gradient norm before clipping, [6] 1 - beta1^t, [7] 1 - beta2^t.
+ * All flat buffers hold n floats and are 16-byte aligned, as is the workspace of uz_tail_workspace_bytes() bytes.
+ * UZ_EINVAL before any launch: a null or misaligned pointer, n <= 0, a number that is not finite, an unknown sched,
+ *   warmup_steps < 0, total_steps <= warmup_steps (cosine, poly), power <= 0 (poly), every < 1 or gamma outside (0, 1] (step),
+ *   accumulate < 1, ema_decay outside [0, 1) with ema.
+ * ------------------------------------------------------------------------------------------- */
+enum { UZ_SCHED_CONSTANT = 0, UZ_SCHED_COSINE = 1, UZ_SCHED_POLY = 2, UZ_SCHED_STEP = 3 };
+typedef struct uz_tail_desc {
+  long long n;            /* elements of every flat buffer */
+  float beta1, beta2, eps, weight_decay, max_norm;   /* as uz_clip_adamw; max_norm <= 0: no clipping */
+  int   sched;            /* UZ_SCHED_* */
+  float warmup_steps, warmup_start, total_steps, min_lr, power, gamma, every;
+  float ema_decay;        /* used when ema != NULL */
+  int   ema_warmup;       /* 1: d_t = min(ema_decay, (1 + t) / (10 + t)) */
+  int   accumulate;       /* k >= 1: the gradient is (g + acc) / k when acc != NULL, else g */
+} uz_tail_desc;
+long long uz_tail_workspace_bytes(void);
+int uz_tail_step(const uz_tail_desc* d, float* p, const float* g, const float* acc /* nullable */, float* m, float* v,
+                 float* ema /* nullable */, float* state, void* workspace, void* stream);
+/* acc = first ? g : acc + g over n floats (one launch); with first != 0 the previous contents of acc are not read */
+int uz_tail_accumulate(float* acc, const float* g, long long n, int first, void* stream);
+/* the CONTENTS of a and b exchanged (one launch); the buffers must not overlap */
+int uz_tail_swap(float* a, float* b, long long n, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * MISSFormer / MiT blocks (unet_zoo/models/missformer.py).  uz_mit.hip
  * ------------------------------------------------------------------------------------------- */
 /* nn.GELU() (erf form) of MixFFN_skip (missformer.py:196,206) on a (P, C) token tensor */

@@ -13,6 +13,7 @@ from .boundary import BoundaryLoss
 from .lovasz import LovaszLoss
 from .augment import GpuAugment
 from .patches import PatchSampler
+from .schedule import LrSchedule
 from .surface import SurfaceMetrics
 from .postprocess import MaskPostprocess
 from .predict import GraphedPredict
@@ -21,6 +22,6 @@ from .config import Config, load_config
 
 __version__ = "0.1.0"
 __all__ = ["create_model", "list_models", "get_model_config", "hip_models", "set_default_dtype",
-           "get_default_dtype", "GraphedStep", "GraphedEval", "RegionLoss", "MulticlassLoss", "BoundaryLoss", "LovaszLoss", "GpuAugment", "PatchSampler", "SurfaceMetrics",
+           "get_default_dtype", "GraphedStep", "GraphedEval", "RegionLoss", "MulticlassLoss", "BoundaryLoss", "LovaszLoss", "GpuAugment", "PatchSampler", "LrSchedule", "SurfaceMetrics",
            "MaskPostprocess", "GraphedPredict", "SlidingWindowPredict",
            "Config", "load_config"]

@@ -44,6 +44,7 @@ EXPORTS = (
     "uz_colsum_workspace_bytes", "uz_colsum_ws", "uz_colstats_rows", "uz_colstats", "uz_cpb_fwd", "uz_cpb_bwd",
     "uz_cpb_fwd_batched", "uz_cpb_bwd_batched_workspace_bytes", "uz_cpb_bwd_batched",
     "uz_clip_adamw_workspace_bytes", "uz_clip_adamw",
+    "uz_tail_workspace_bytes", "uz_tail_step", "uz_tail_accumulate", "uz_tail_swap",
     "uz_gelu_fwd", "uz_gelu_bwd", "uz_dwconv3x3", "uz_dwconv3x3_wgrad_rows", "uz_dwconv3x3_wgrad",
     "uz_space_to_depth", "uz_space_to_depth_crop", "uz_im2col_nchw", "uz_sra_fwd", "uz_sra_bwd_workspace_bytes", "uz_sra_bwd",
     "uz_bce_dice_workspace_bytes", "uz_bce_dice", "uz_colsum_batched_workspace_bytes", "uz_colsum_batched", "uz_sum_rows_f32_batched", "uz_conv_igemm_res", "uz_wgrad_multi_workspace_bytes", "uz_wgrad_multi", "uz_conv_igemm_res_ws",
@@ -230,6 +231,19 @@ class BoundaryDesc(Structure):
         + [("spacing", c_float)]
 
 
+SCHED_CONSTANT, SCHED_COSINE, SCHED_POLY, SCHED_STEP = range(4)     # UZ_SCHED_*
+TAIL_STATE = 8                                                      # floats of uz_tail_step's `state`
+TAIL_T, TAIL_BASE_LR, TAIL_LR, TAIL_EMA_DECAY, TAIL_CLIP, TAIL_NORM, TAIL_BC1, TAIL_BC2 = range(8)
+
+
+class TailDesc(Structure):
+    """uz_tail_desc"""
+    _fields_ = [("n", ctypes.c_longlong)] + [(n, c_float) for n in ("beta1", "beta2", "eps", "weight_decay", "max_norm")] \
+        + [("sched", c_int)] \
+        + [(n, c_float) for n in ("warmup_steps", "warmup_start", "total_steps", "min_lr", "power", "gamma", "every", "ema_decay")] \
+        + [("ema_warmup", c_int), ("accumulate", c_int)]
+
+
 LOVASZ_BINARY, LOVASZ_CLASS = 0, 1
 LOVASZ_PRESENT, LOVASZ_ALL = 0, 1
 LOVASZ_MAX_SEGMENT = 1 << 22
@@ -341,6 +355,10 @@ def load():
     lib.uz_cpb_bwd_batched.argtypes = [vp, ip, vp, vp]
     lib.uz_clip_adamw_workspace_bytes.argtypes = []
     lib.uz_clip_adamw.argtypes = [vp, vp, vp, vp, ctypes.c_longlong, fp, fp, fp, fp, fp, fp, vp, vp, vp]
+    lib.uz_tail_workspace_bytes.argtypes = []
+    lib.uz_tail_step.argtypes = [POINTER(TailDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.uz_tail_accumulate.argtypes = [vp, vp, ctypes.c_longlong, ip, vp]
+    lib.uz_tail_swap.argtypes = [vp, vp, ctypes.c_longlong, vp]
     lib.uz_wgrad_split.argtypes = [POINTER(WgradDesc)]
     lib.uz_wgrad_workspace_bytes.argtypes = [POINTER(WgradDesc)]
     lib.uz_wgrad.argtypes = [POINTER(WgradDesc), vp, vp, vp, vp, vp]

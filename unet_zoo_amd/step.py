@@ -46,9 +46,28 @@ front of the augmentation's when there is one, which then reads the sampler's st
 draws its own patches (``step.sampled``, ``step.coords``) and the host does nothing per step.  The dry run that plans the graphs
 needs real patches, so ONE set of draws is consumed before the capture (with ``force_draws(u)`` that is not sticky, the forced
 ones).  With several ranks each rank holds its own pool and draws from its own generator.  Without ``source`` nothing changes.
+
+The scheduled tail: ``GraphedStep(model, schedule=LrSchedule.cosine(10_000, warmup_steps=500), ema=0.999, accumulate=2)``.  Any of
+``schedule`` / ``ema`` / ``accumulate`` replaces the last hipGraph's three launches by ``optim.FlatTail``'s (``uz_steptail.hip``):
+the same clip + AdamW arithmetic, with the step counter, the BASE rate and the rate in use in a device state.
+* ``schedule``: the prepare launch evaluates the schedule from the device's counter, every replay at its own rate; ``set_lr(lr)``
+  fills the base rate on the stream -- no synchronize, no new capture; ``step.lr_now`` is the rate the last step used.
+* ``ema``: an averaged copy of the weights, updated in the apply launch (``ema_warmup``: decay ``min(ema, (1 + t) / (10 + t))``);
+  ``with step.ema_weights():`` exchanges its contents with the parameters' for evaluation and saving.  BatchNorm running
+  statistics are module buffers: shared, not averaged.
+* ``accumulate=k``: one optimizer step takes k calls of ``step(x, t)``; calls 1 .. k-1 replay the forward / backward graphs and add
+  the gradient to an accumulator (one eager launch), call k replays a tail that consumes ``(flat_g + acc) / k``.  Every call
+  returns its own micro-batch loss, ``grad_norm`` is the norm of the mean gradient, ``steps_done`` counts optimizer steps, BatchNorm
+  running statistics advance per micro-batch as in torch.  With several ranks the per-phase all-reduce runs in EVERY micro-step:
+  the mean is linear, so the result is right, but k - 1 of the k exchanges could be saved -- not optimised.
+* ``step.state_dict()`` / ``load_state_dict()``: the moments, the counter, the rate, the position inside an accumulation and the
+  EMA / accumulator buffers by parameter name -- with ``checkpoint.save_model_state`` a run resumes bit for bit (both tails).
+With all of them at their defaults nothing changes: the same class, the same graphs, ``set_lr`` captures the tail again.
 """
 from __future__ import annotations
 
+import contextlib
+from collections import OrderedDict
 from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
@@ -60,7 +79,8 @@ from .augment import GpuAugment
 from .patches import PatchSampler
 from .capture import CAPTURE_MODE, _check_capture, _new_graph, _unwrap, resolve_criterion, static_copy, unchanged
 from .criterion import FusedCriterion
-from .optim import FlatClipAdamW
+from .optim import FlatClipAdamW, FlatTail, check_tail_args
+from .schedule import LrSchedule
 
 
 class _ShapeGraphs:
@@ -75,8 +95,12 @@ class GraphedStep:
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-5,
                  max_norm: float = 1.0, phases: int = 5, process_group=None, data_parallel: Optional[bool] = None,
                  cu_reserve: Optional[int] = None, comm: str = "overlap", comm_dtype: Optional[torch.dtype] = None,
-                 augment: Optional[GpuAugment] = None, source: Optional[PatchSampler] = None):
-        """augment: a GpuAugment applied to every batch inside the first graph (module docstring); every rank draws from its own
+                 augment: Optional[GpuAugment] = None, source: Optional[PatchSampler] = None,
+                 schedule: Optional[LrSchedule] = None, ema: Optional[float] = None, ema_warmup: bool = True,
+                 accumulate: int = 1):
+        """schedule / ema / ema_warmup / accumulate: the scheduled step tail (module docstring); with all four at their defaults
+        the tail is FlatClipAdamW as before.
+        augment: a GpuAugment applied to every batch inside the first graph (module docstring); every rank draws from its own
         generator.
         source: a PatchSampler whose patches ARE the batch: the step is then called without arguments (module docstring).
         comm: when the gradient exchange of a data-parallel step runs -- "overlap": the span of every finished backward
@@ -116,6 +140,13 @@ class GraphedStep:
                              "targets (class indices go with MulticlassLoss, fp32 masks with every other criterion)")
         self.source = source
         self.lr, self.betas, self.eps, self.weight_decay, self.max_norm = lr, betas, eps, weight_decay, max_norm
+        check_tail_args(schedule, ema, accumulate)
+        self.schedule, self.ema_decay, self.ema_warmup, self.accumulate = schedule, ema, bool(ema_warmup), accumulate
+        # any of the three given: the tail is FlatTail (uz_steptail.hip); none: FlatClipAdamW, exactly as before
+        self._tail = schedule is not None or ema is not None or accumulate != 1
+        self._micro = 0                      # micro-batches already accumulated towards the next optimizer step
+        self._in_ema = False                 # inside `with step.ema_weights():`
+        self._pending_state: Optional[dict] = None
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         # data_parallel=True with one rank keeps the multi-rank launch strategy (phases + collectives): a rehearsal
@@ -171,8 +202,13 @@ class GraphedStep:
         ordered = [p for grp in groups for p in grp]
         if not ordered:
             raise RuntimeError("no parameter received a gradient")
-        self.opt = FlatClipAdamW(ordered, lr=self.lr, betas=self.betas, eps=self.eps,
-                                 weight_decay=self.weight_decay, max_norm=self.max_norm)
+        if self._tail:
+            self.opt = FlatTail(ordered, lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
+                                max_norm=self.max_norm, schedule=self.schedule, ema=self.ema_decay, ema_warmup=self.ema_warmup,
+                                accumulate=self.accumulate)
+        else:
+            self.opt = FlatClipAdamW(ordered, lr=self.lr, betas=self.betas, eps=self.eps,
+                                     weight_decay=self.weight_decay, max_norm=self.max_norm)
         # the parameters moved into the flat buffer: new pointer tables, built outside any capture
         m._pack_cache.repoint()
         m._pack_cache.refresh(m.run_dtype)
@@ -190,6 +226,9 @@ class GraphedStep:
             self._broadcast(self.opt.flat_p)
             for b in m.buffers():
                 self._broadcast(b)
+        if self._pending_state is not None:      # a load_state_dict() from before the flat buffers existed
+            state, self._pending_state = self._pending_state, None
+            self._apply_state(state)
         self._capture_opt()
 
     def _capture_opt(self) -> None:
@@ -199,10 +238,15 @@ class GraphedStep:
         _check_capture(self._g_opt, "optimizer graph")
 
     def set_lr(self, lr: float) -> None:
-        """Learning-rate change (the reference's DiceScheduler, utils/lr_scheduler.py:70-81): the rate is a kernel
-        argument, so the three-launch optimizer graph is captured again."""
+        """Learning-rate change (the reference's DiceScheduler, utils/lr_scheduler.py:70-81).  Default tail: the rate is a
+        kernel argument, so the three-launch optimizer graph is captured again.  Scheduled tail: the BASE rate of the
+        schedule is one device float (state[1]); it is filled on the stream -- no synchronize, no new capture."""
         self.lr = lr
-        if self.opt is not None:
+        if self.opt is None:
+            return
+        if self._tail:
+            self.opt.set_lr(lr)
+        else:
             self.opt.lr = lr
             torch.cuda.synchronize()
             self._capture_opt()
@@ -345,6 +389,7 @@ class GraphedStep:
         """zero_grad + forward + loss + backward (+ gradient all-reduce): afterwards every ``p.grad`` (views of the flat
         buffer) holds this step's (rank-averaged) gradient.  Returns the loss as a device scalar.  With `source` the batch
         is the sampler's and no argument is taken."""
+        self._refuse_in_ema()
         if self.source is not None:
             if x is not None or target is not None:
                 raise TypeError("this GraphedStep draws its batch from `source` (a PatchSampler): call it without arguments")
@@ -446,18 +491,138 @@ class GraphedStep:
 
     def optimizer_step(self) -> None:
         """clip_grad_norm_(max_norm) + AdamW on the flat buffers (training_loop.py:120-121)"""
+        self._refuse_in_ema()
         self._g_opt.replay()
         self.steps_done += 1
+        self._micro = 0
+
+    def accumulate_gradient(self) -> None:
+        """`accumulate` > 1, after forward_backward() of one of the first k - 1 micro-batches: add its gradient to the
+        accumulator (uz_tail_accumulate, one eager launch; the first of a group overwrites what the accumulator held)"""
+        self._refuse_in_ema()
+        if self._micro + 1 >= self.accumulate:
+            raise RuntimeError(f"accumulate={self.accumulate}: {self._micro} micro-batches are accumulated, the next call is optimizer_step()")
+        self.opt.accumulate_grad(self._micro == 0)
+        self._micro += 1
 
     def __call__(self, x: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One call of the training loop.  With accumulate = k > 1 it is one MICRO-batch: calls 1 .. k-1 of a group run forward +
+        backward and add the gradient to the accumulator, call k runs the optimizer tail on the mean of the k gradients;
+        every call returns its own micro-batch's loss."""
         loss = self.forward_backward(x, target)
-        self.optimizer_step()
+        if self._micro + 1 < self.accumulate:
+            self.accumulate_gradient()
+        else:
+            self.optimizer_step()
         return loss
+
+    # ------------------------------------------------------------------ the scheduled tail: EMA weights, state
+    def _refuse_in_ema(self) -> None:
+        if self._in_ema:
+            raise RuntimeError("inside `with step.ema_weights():` the parameters ARE the averaged weights: no training step, "
+                               "no state_dict() -- leave the context first")
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with step.ema_weights():`` -- evaluate, predict or save with the averaged weights.  The CONTENTS of the flat
+        parameter buffer and of the EMA buffer are exchanged on entry and again on exit (uz_tail_swap, one launch each): no
+        address moves, every captured graph stays valid, and since every forward begins with the pack cache's re-pack launch a
+        following GraphedEval / GraphedPredict / model(x) / checkpoint.save_model_state sees the averaged weights.  Module
+        BUFFERS (the BatchNorm running statistics) are shared, not averaged.  Training inside the context raises."""
+        if self.ema_decay is None:
+            raise RuntimeError("this GraphedStep keeps no averaged weights: build it with ema=<decay>")
+        if self.opt is None:
+            raise RuntimeError("ema_weights(): the averaged weights exist from the first training step on")
+        if self._in_ema:
+            raise RuntimeError("ema_weights() is not re-entrant")
+        self.opt.swap_ema()
+        self._in_ema = True
+        try:
+            yield self
+        finally:
+            self.opt.swap_ema()
+            self._in_ema = False
+
+    @property
+    def lr_now(self) -> torch.Tensor:
+        """the rate the last optimizer step used, a device scalar (scheduled tail: state[2], the schedule's value)"""
+        if self._tail:
+            return self.opt.last_lr()
+        return torch.tensor(self.lr, dtype=torch.float32, device=self.opt.flat_p.device)
+
+    def _param_names(self) -> List[str]:
+        names = {id(p): n for n, p in self.model.named_parameters()}
+        return [names[id(p)] for p in self.opt.params]
+
+    def state_dict(self) -> dict:
+        """What a resume needs beside the model's own state_dict (checkpoint.save_model_state): "step" (optimizer steps done),
+        "lr" (the base rate), "micro" (micro-batches already accumulated towards the next step), "schedule" (the schedule's
+        numbers, None without one; a record -- a resumed step keeps the schedule it was built with) and "state": by parameter
+        name, detached clones of exp_avg, exp_avg_sq and, where the tail has them, ema and acc.  Reads the step counter: one
+        host synchronize."""
+        self._refuse_in_ema()
+        if self.opt is None:
+            raise RuntimeError("state_dict(): the optimizer state exists from the first training step on")
+        opt = self.opt
+        bufs = {"exp_avg": opt.exp_avg, "exp_avg_sq": opt.exp_avg_sq}
+        for k in ("ema", "acc"):
+            if getattr(opt, k, None) is not None:
+                bufs[k] = getattr(opt, k)
+        state = OrderedDict()
+        for name, p, (a0, _) in zip(self._param_names(), opt.params, opt.spans):
+            state[name] = {k: b[a0:a0 + p.numel()].view_as(p).detach().clone() for k, b in bufs.items()}
+        return {"step": int(opt.step_count.item()), "lr": float(self.lr), "micro": self._micro,
+                "schedule": self.schedule.numbers() if self.schedule is not None else None, "state": state}
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Restore a state_dict() of a step built with the same arguments on the same model.  Before the first call the state
+        is kept and applied at the end of the set-up (the flat buffers do not exist until then); parameter names or buffers
+        that do not match raise."""
+        for k in ("step", "lr", "micro", "state"):
+            if k not in sd:
+                raise KeyError(f"load_state_dict: no {k!r} in the state")
+        if not 0 <= int(sd["micro"]) < self.accumulate:
+            raise ValueError(f"load_state_dict: micro={sd['micro']} does not fit accumulate={self.accumulate}")
+        if self.opt is None:
+            self._pending_state = sd
+        else:
+            self._refuse_in_ema()
+            self._apply_state(sd)
+
+    def _apply_state(self, sd: dict) -> None:
+        opt, names = self.opt, self._param_names()
+        if set(names) != set(sd["state"]):
+            odd = sorted(set(names) ^ set(sd["state"]))
+            raise KeyError(f"load_state_dict: parameter names do not match: {odd[:6]}{' ...' if len(odd) > 6 else ''}")
+        bufs = {"exp_avg": opt.exp_avg, "exp_avg_sq": opt.exp_avg_sq}
+        for k in ("ema", "acc"):
+            if getattr(opt, k, None) is not None:
+                bufs[k] = getattr(opt, k)
+        for name, p, (a0, _) in zip(names, opt.params, opt.spans):
+            ent = sd["state"][name]
+            if set(ent) != set(bufs):
+                raise KeyError(f"load_state_dict: {name} holds {sorted(ent)}, this step's tail keeps {sorted(bufs)}")
+            for k, b in bufs.items():
+                if tuple(ent[k].shape) != tuple(p.shape):
+                    raise ValueError(f"load_state_dict: {name}.{k} has shape {tuple(ent[k].shape)}, the parameter {tuple(p.shape)}")
+                b[a0:a0 + p.numel()].view_as(p).copy_(ent[k])
+        opt.step_count.fill_(float(sd["step"]))
+        self.steps_done, self._micro = int(sd["step"]), int(sd["micro"])
+        lr = float(sd["lr"])
+        if self._tail:
+            self.lr = lr
+            opt.set_lr(lr)
+        elif lr != opt.lr:
+            self.lr = opt.lr = lr
+            if self._g_opt is not None:          # the rate is an argument of the captured launches
+                torch.cuda.synchronize()
+                self._capture_opt()
 
     # ------------------------------------------------------------------ introspection
     @property
     def grad_norm(self) -> torch.Tensor:
-        """total gradient norm the last optimizer step saw, before clipping (device scalar)"""
+        """total gradient norm the last optimizer step saw, before clipping (device scalar); with accumulate > 1 the norm of
+        the MEAN gradient"""
         return self.opt.last_grad_norm()
 
     @property
@@ -487,7 +652,14 @@ class GraphedStep:
     def describe(self) -> str:
         """launch strategy in words (bench.py's `launch` field)"""
         k = len(self._cuts) - 1 if self._cuts else self.n_phases
-        opt = "hipGraph(clip+AdamW on flat buffers, 3 launches)"
+        tail = []
+        if self.schedule is not None:
+            tail.append(f"{self.schedule.kind} schedule")
+        if self.ema_decay is not None:
+            tail.append("EMA")
+        if self.accumulate > 1:
+            tail.append(f"mean of {self.accumulate} accumulated gradients")
+        opt = f"hipGraph({'+'.join(['clip', 'AdamW'] + tail)} on flat buffers, 3 launches)"
         crit = "" if self._fused_loss else "hipGraph(fwd) + eager criterion + "
         head = [name for name, opt_in in (("PatchSampler", self.source), ("GpuAugment", self.augment)) if opt_in is not None]
         if head:
