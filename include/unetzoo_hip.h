@@ -1210,6 +1210,57 @@ int uz_surface_metrics(const uz_surface_desc* d, const float* logits, const void
                        void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Confusion counts of a thresholded prediction against its target, per (image, class) pair, and the overlap scores derived
+ * from them; in the binary mode also the score histograms that ROC / PR curves are summed from.  Everything counted is an
+ * integer: exact, independent of the order of arrival and of the grid, summable over a pass.  uz_confusion.hip
+ * UZ_CONFUSION_BINARY: logits and target (N, C, H, W) fp32; every (image, channel) plane is a pair: P = C.
+ *   prediction x > 0, target t > 0.5 (the thresholds of uz_bce_dice and uz_surface): x = 0 is negative, t = 0.5 is negative,
+ *   a NaN logit is negative.
+ *   counts (N, P, 4) int64 = TP, FP, FN, TN
+ *   hist   (N, P, 2, B) int64: hist[n, p, s, b] = pixels with (t > 0.5) == s and bin(x) == b, where
+ *          bin(x) = the number of edges e_k with x >= e_k   -- numpy.searchsorted(edges, x, side="right"); NaN: bin 0
+ *   edges  B - 1 floats ON THE DEVICE, strictly ascending and finite, IN LOGIT SPACE: the kernel compares floats against the
+ *          table and evaluates no sigmoid.  Their contents are the caller's responsibility (a host check would read device
+ *          memory); a table that is not ascending gives a histogram that means nothing, never an access out of bounds.
+ * UZ_CONFUSION_CLASS : logits (N, C, H, W) fp32 with C = K classes, target (N, H, W) int32 labels; prediction argmax_K, ties
+ *   to the lowest index (as uz_class_loss and uz_surface).  A pixel whose label is ignore_index or outside [0, K) is counted
+ *   nowhere.
+ *   counts (N, K, K) int64: counts[n, t, p] = pixels with label t and prediction p
+ *   hist and edges are not used (NULL), bins = 0.  Pairs are the classes first_class .. K - 1: P = K - first_class, with
+ *   TP = counts[c, c], FP = column sum - TP, FN = row sum - TP, TN = valid pixels - TP - FP - FN.
+ * out (N, P, 8) fp32 = dice, iou, precision, recall, specificity, state, 0, 0 per pair:
+ *   dice = 2 TP / (2 TP + FP + FN), iou = TP / (TP + FP + FN), precision = TP / (TP + FP), recall = TP / (TP + FN),
+ *   specificity = TN / (TN + FP); every score is ONE float64 division of integers, rounded to float32 once; a score whose
+ *   denominator is 0 is 0, except dice = iou = 1 in state 3
+ *   state = 0 both masks non-empty, 1 the prediction empty, 2 the target empty, 3 both empty (as uz_surface)
+ * One call is THREE launches whatever the shape (clear, count, finalize), no allocation, no memset, no host
+ * synchronisation; the workspace (uz_confusion_workspace_bytes, 16-byte aligned, int32 counters: a plane has at most 2^24
+ * pixels) is cleared by the first launch.  The counting pass gives every workgroup one contiguous run of (plane, tile) units
+ * (a tile: 1024 consecutive pixels of a plane, in the class mode of an image), counts into a histogram in LDS and adds its
+ * non-zero bins to the workspace with integer atomics when the run leaves a plane and at its end.  uz_confusion_grid()
+ * returns the workgroups of the counting pass and (units, nullable) the units they share out: units > workgroups means
+ * workgroups walk.  max_workgroups > 0 caps the grid.
+ * UZ_EINVAL before any launch: null descriptor / pointer (edges and hist: binary mode only), unknown mode, N, C, H or W < 1,
+ * H or W > 4096, N C H W >= 2^31, in the class mode K outside [2, UZ_CLASS_MAX_K], first_class outside [0, K) or bins != 0,
+ * in the binary mode bins not a power of two in [16, 1024], max_workgroups < 0, tensors misaligned (4 bytes; counts and hist
+ * 8, workspace 16) or overlapping. */
+#define UZ_CONFUSION_BINARY 0
+#define UZ_CONFUSION_CLASS 1
+typedef struct uz_confusion_desc {
+  int mode;           /* UZ_CONFUSION_* */
+  int N, C, H, W;     /* C: channels (binary) or classes K (class mode) */
+  int first_class;    /* class mode: the first class that is a pair (1 leaves the background out) */
+  int ignore_index;   /* class mode */
+  int bins;           /* binary mode: B, a power of two in [16, 1024]; class mode: 0 */
+  int max_workgroups; /* 0: the plan's own grid; > 0: cap it (CU sharing; lets a small shape walk) */
+  int reserved[3];
+} uz_confusion_desc;
+long long uz_confusion_workspace_bytes(const uz_confusion_desc* d); /* < 0: refused */
+int uz_confusion_grid(const uz_confusion_desc* d, int* units /* nullable */);
+int uz_confusion_metrics(const uz_confusion_desc* d, const float* logits, const void* target, const float* edges /* binary: B - 1 */,
+                         long long* counts, long long* hist /* binary */, float* out, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Boundary loss (Kervadec et al., "Boundary loss for highly unbalanced segmentation") on top of a base loss whose value
  * and gradients exist already: the exact signed Euclidean distance transform of the target, dense, and the mean of
  * probability x signed distance over several output maps.  uz_boundary_loss.hip

@@ -15,6 +15,7 @@ from .augment import GpuAugment
 from .patches import PatchSampler
 from .schedule import LrSchedule
 from .surface import SurfaceMetrics
+from .confusion import ConfusionMetrics
 from .postprocess import MaskPostprocess
 from .predict import GraphedPredict
 from .tiled import SlidingWindowPredict
@@ -22,6 +23,6 @@ from .config import Config, load_config
 
 __version__ = "0.1.0"
 __all__ = ["create_model", "list_models", "get_model_config", "hip_models", "set_default_dtype",
-           "get_default_dtype", "GraphedStep", "GraphedEval", "RegionLoss", "MulticlassLoss", "BoundaryLoss", "LovaszLoss", "GpuAugment", "PatchSampler", "LrSchedule", "SurfaceMetrics",
+           "get_default_dtype", "GraphedStep", "GraphedEval", "RegionLoss", "MulticlassLoss", "BoundaryLoss", "LovaszLoss", "GpuAugment", "PatchSampler", "LrSchedule", "SurfaceMetrics", "ConfusionMetrics",
            "MaskPostprocess", "GraphedPredict", "SlidingWindowPredict",
            "Config", "load_config"]

@@ -60,6 +60,7 @@ EXPORTS = (
     "uz_augment_params", "uz_augment_grid", "uz_augment_apply",
     "uz_patch_index_bytes", "uz_patch_index", "uz_patch_draw", "uz_patch_cut_grid", "uz_patch_cut",
     "uz_surface_workspace_bytes", "uz_surface_grid", "uz_surface_metrics",
+    "uz_confusion_workspace_bytes", "uz_confusion_grid", "uz_confusion_metrics",
     "uz_boundary_workspace_bytes", "uz_boundary_grid", "uz_boundary_loss",
     "uz_lovasz_workspace_bytes", "uz_lovasz_grid", "uz_lovasz_loss",
     "uz_postproc_workspace_bytes", "uz_postproc_grid", "uz_postproc",
@@ -214,6 +215,17 @@ class SurfaceDesc(Structure):
     """uz_surface_desc"""
     _fields_ = [(n, c_int) for n in ("mode", "N", "C", "H", "W", "first_class", "ignore_index", "reserved")] \
         + [("q", c_double), ("spacing", c_double)]
+
+
+CONFUSION_BINARY, CONFUSION_CLASS = 0, 1
+CONFUSION_MAX_HW = 4096
+CONFUSION_MIN_BINS, CONFUSION_MAX_BINS = 16, 1024
+
+
+class ConfusionDesc(Structure):
+    """uz_confusion_desc"""
+    _fields_ = [(n, c_int) for n in ("mode", "N", "C", "H", "W", "first_class", "ignore_index", "bins", "max_workgroups")] \
+        + [("reserved", c_int * 3)]
 
 
 BOUNDARY_BINARY, BOUNDARY_CLASS = 0, 1
@@ -488,6 +500,9 @@ def load():
     lib.uz_surface_workspace_bytes.argtypes = [POINTER(SurfaceDesc)]
     lib.uz_surface_grid.argtypes = [POINTER(SurfaceDesc), POINTER(c_int)]
     lib.uz_surface_metrics.argtypes = [POINTER(SurfaceDesc), vp, vp, vp, vp, vp, vp]
+    lib.uz_confusion_workspace_bytes.argtypes = [POINTER(ConfusionDesc)]
+    lib.uz_confusion_grid.argtypes = [POINTER(ConfusionDesc), POINTER(c_int)]
+    lib.uz_confusion_metrics.argtypes = [POINTER(ConfusionDesc), vp, vp, vp, vp, vp, vp, vp, vp]
     lib.uz_boundary_workspace_bytes.argtypes = [POINTER(BoundaryDesc)]
     lib.uz_boundary_grid.argtypes = [POINTER(BoundaryDesc), POINTER(c_int)]
     lib.uz_boundary_loss.argtypes = [POINTER(BoundaryDesc), POINTER(BoundaryItem), vp, vp, vp, vp, vp, vp, vp]
@@ -577,6 +592,28 @@ def surface_metrics(desc: "SurfaceDesc", logits: torch.Tensor, target: torch.Ten
     """uz_surface_metrics() on the current stream: seven launches, no allocation, no host read"""
     check(load().uz_surface_metrics(ctypes.byref(desc), logits.data_ptr(), target.data_ptr(), out.data_ptr(), stats.data_ptr(),
                                     workspace.data_ptr(), stream_ptr()), "uz_surface_metrics")
+
+
+def confusion_workspace_bytes(desc: "ConfusionDesc") -> int:
+    """uz_confusion_workspace_bytes(): bytes of workspace a uz_confusion_metrics call with this descriptor needs"""
+    return check_count(load().uz_confusion_workspace_bytes(ctypes.byref(desc)), "uz_confusion_workspace_bytes")
+
+
+def confusion_grid(desc: "ConfusionDesc") -> tuple:
+    """uz_confusion_grid(): (workgroups, units) of the counting pass of uz_confusion_metrics for this descriptor"""
+    units = c_int(0)
+    grid = check_count(load().uz_confusion_grid(ctypes.byref(desc), ctypes.byref(units)), "uz_confusion_grid")
+    return grid, units.value
+
+
+def confusion_metrics(desc: "ConfusionDesc", logits: torch.Tensor, target: torch.Tensor, edges, counts: torch.Tensor, hist,
+                      out: torch.Tensor, workspace: torch.Tensor) -> None:
+    """uz_confusion_metrics() on the current stream: three launches, no allocation, no host read; edges and hist are None in
+    the class mode"""
+    check(load().uz_confusion_metrics(ctypes.byref(desc), logits.data_ptr(), target.data_ptr(),
+                                      edges.data_ptr() if edges is not None else None, counts.data_ptr(),
+                                      hist.data_ptr() if hist is not None else None, out.data_ptr(), workspace.data_ptr(),
+                                      stream_ptr()), "uz_confusion_metrics")
 
 
 def boundary_workspace_bytes(desc: "BoundaryDesc") -> int:

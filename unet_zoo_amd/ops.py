@@ -1756,6 +1756,40 @@ def surface_metrics(desc: "L.SurfaceDesc", logits: torch.Tensor, target: torch.T
         L.surface_metrics(desc, logits, target, out, stats, workspace)
 
 
+# ---- ConfusionMetrics: confusion counts, score histograms and overlap scores (uz_confusion.hip) -------------------------------
+def confusion_grid(desc: "L.ConfusionDesc") -> tuple:
+    """(workgroups, units) of the counting pass of uz_confusion_metrics for this descriptor: units > workgroups means
+    workgroups walk"""
+    return L.confusion_grid(desc)
+
+
+def confusion_metrics(desc: "L.ConfusionDesc", logits: torch.Tensor, target: torch.Tensor, edges: Optional[torch.Tensor],
+                      counts: torch.Tensor, hist: Optional[torch.Tensor], out: torch.Tensor, workspace: torch.Tensor) -> None:
+    """counts int64 ((N, C, 4) = TP, FP, FN, TN, or the (N, K, K) matrices), hist (N, C, 2, B) int64 (binary mode) and out
+    (N, P, 8) fp32 = dice, iou, precision, recall, specificity, state, 0, 0 <- logits (N, C, H, W) fp32 against target: fp32
+    (N, C, H, W) maps with the B - 1 fp32 logit-space edges (UZ_CONFUSION_BINARY) or int32 (N, H, W) labels
+    (UZ_CONFUSION_CLASS); three launches"""
+    cls = desc.mode == L.CONFUSION_CLASS
+    tensors = (logits, target, counts, out, workspace) + (() if cls else (edges, hist))
+    L.require_cuda(*tensors)
+    for t in tensors:
+        assert t.is_contiguous()
+    P = desc.C - desc.first_class if cls else desc.C
+    assert logits.dtype == out.dtype == torch.float32 and counts.dtype == torch.int64
+    assert target.dtype == (torch.int32 if cls else torch.float32)
+    assert tuple(logits.shape) == (desc.N, desc.C, desc.H, desc.W)
+    assert tuple(target.shape) == ((desc.N, desc.H, desc.W) if cls else tuple(logits.shape))
+    assert tuple(out.shape) == (desc.N, P, 8)
+    if cls:
+        assert edges is None and hist is None and tuple(counts.shape) == (desc.N, desc.C, desc.C)
+    else:
+        assert edges.dtype == torch.float32 and tuple(edges.shape) == (desc.bins - 1,)
+        assert hist.dtype == torch.int64 and tuple(hist.shape) == (desc.N, desc.C, 2, desc.bins)
+        assert tuple(counts.shape) == (desc.N, desc.C, 4)
+    with _Timed("confusion_metrics", 0.0, 4.0 * (logits.numel() + target.numel())):
+        L.confusion_metrics(desc, logits, target, edges, counts, hist, out, workspace)
+
+
 # ---- BoundaryLoss: signed distance transform of the target + the boundary term (uz_boundary_loss.hip) -------------------------
 def boundary_grid(desc: "L.BoundaryDesc") -> tuple:
     """(workgroups, units) of the column pass of uz_boundary_loss for this descriptor: units > workgroups means workgroups
