@@ -1376,6 +1376,68 @@ int uz_lovasz_loss(const uz_lovasz_desc* d, const uz_lovasz_item* items, const v
                    void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * clDice (Shit et al., "clDice -- a novel topology-preserving loss function for tubular structure segmentation", CVPR 2021)
+ * on top of a base loss whose value and gradients exist already: the soft skeleton as a stencil held in LDS.
+ * uz_cldice_loss.hip
+ * For a plane a (H, W), every window clipped to the picture:
+ *   erode(a) = min(v, h): v the minimum of the vertical 3-window (up, centre, down), h of the horizontal one (left, centre,
+ *   right);  dilate(a) = the maximum of the 3 x 3 window;  open(a) = dilate(erode(a));
+ *   skel_k(a): S = relu(a - open(a)); then k times: a <- erode(a), d = relu(a - open(a)), S <- S + relu(d - S d).
+ * skel_k(a) at a pixel depends on a within Chebyshev distance R = k + 2; k = iterations.  For one segment, with prediction
+ * plane(s) p, target plane(s) t and s = smooth > 0:
+ *   Tprec = (sum skel(p) t + s) / (sum skel(p) + s),  Tsens = (sum skel(t) p + s) / (sum skel(t) + s),
+ *   cl = 1 - 2 Tprec Tsens / (Tprec + Tsens);   V = the mean of cl over the segments.
+ * UZ_CLDICE_BINARY: logits and target (N, C, H, W) fp32; p = sigmoid(x) in fp32, t the target as given (soft values in
+ *   [0, 1] allowed; skel(t) gets no gradient).  per_image = 0: a segment per channel over the batch; 1: per (image, channel).
+ * UZ_CLDICE_CLASS : logits (N, C, H, W) fp32 with C = K classes, target (N, H, W) int32 labels y; p = softmax_K(x),
+ *   t_c = (y == c); the classes are 1 .. K-1, or 0 .. K-1 with include_background.  A pixel whose label is ignore_index or
+ *   outside [0, K) has p_c = t_c = 0 in every plane before the skeleton, whatever gradient reaches it is dropped: its K
+ *   logits get exactly zero.  dV/dx_k = p_k (g_k - sum_c p_c g_c) with g_c = dV/dp_c, 0 for an excluded class.
+ * Subgradients are torch's: relu'(0) = 0; dilate routes to the first maximum in row-major window order; v to the first
+ * minimum top to bottom, h left to right; min(v, h) to the smaller one, half to each on v == h.
+ * scales = {weight, base_scale} and base_loss are ON THE DEVICE, as for uz_lovasz_loss:
+ *   out[0] = base_scale * base_loss + weight * sum_m items[m].weight * V_m;   out[1] = V of map main_item
+ *   items[m].dlogits (nullable): dl <- base_scale * dl + weight * items[m].weight * dV/dx, in place.
+ * probs and skeleton (N, C, H, W) fp32 are OUTPUTS, p and skel(p) of map main_item (an excluded class's skeleton plane is
+ * not written); target_skeleton (N, C, H, W) fp32 is skel(t), computed once per call for all maps.
+ * One call is 4 launches, 6 when a map has a gradient buffer, whatever n_items and the data are: prob, target skeleton,
+ * forward tiles, sums (+ out), [backward tiles, grad].  A tile is UZ_CLDICE_TILE_H x UZ_CLDICE_TILE_W pixels of one plane
+ * with a halo of R (forward) or 2 R (backward, which forms the forward again); a unit is (map, plane, tile).  No allocation,
+ * no memset, no host read, no float atomics, no waiting between workgroups; float64 sums in a fixed order: two calls on the
+ * same inputs give the same bits.  The k + 1 intermediate images of a map stay in LDS.  The workspace holds p and dV/dp of
+ * every map (8 bytes per element) plus, in the class mode, the target's planes.  uz_cldice_grid() returns the workgroups of
+ * the tile passes and (units, nullable) the units they share out: units > workgroups means workgroups walk.
+ * UZ_EINVAL before any launch: the cases of uz_lovasz_loss (no segment limit), iterations outside
+ * [1, UZ_CLDICE_MAX_ITERATIONS], smooth not finite or not positive. */
+#define UZ_CLDICE_BINARY 0
+#define UZ_CLDICE_CLASS 1
+#define UZ_CLDICE_MAX_ITERATIONS 10
+#define UZ_CLDICE_TILE_H 32
+#define UZ_CLDICE_TILE_W 32
+typedef struct uz_cldice_item {
+  const float* logits;
+  float* dlogits; /* nullable; in: the base loss's gradient, out: the combined one */
+  float weight;
+} uz_cldice_item;
+typedef struct uz_cldice_desc {
+  int mode; /* UZ_CLDICE_BINARY / UZ_CLDICE_CLASS */
+  int n_items;
+  int N, C, H, W;         /* C: channels (binary) or classes K (class mode) */
+  int per_image;          /* 0: one segment per channel / class over the whole batch */
+  int include_background; /* class mode: class 0 counts too */
+  int ignore_index;       /* class mode */
+  int iterations;         /* k */
+  float smooth;
+  int main_item;
+} uz_cldice_desc;
+long long uz_cldice_workspace_bytes(const uz_cldice_desc* d); /* < 0: refused */
+int uz_cldice_grid(const uz_cldice_desc* d, int* units /* nullable */);
+int uz_cldice_loss(const uz_cldice_desc* d, const uz_cldice_item* items, const void* target,
+                   const float* scales /* device: weight, base_scale */, const float* base_loss /* device */,
+                   float* out /* 2 */, float* probs /* N C H W, an output */, float* skeleton /* N C H W, an output */,
+                   float* target_skeleton /* N C H W, an output */, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Mask post-processing, per (image, plane), every result an integer that scipy.ndimage gives too.  uz_postproc.hip
  * UZ_POST_BINARY: x (N, C, H, W) fp32; plane = x > thr, every channel a plane: P = C.  Logits with thr = 0 or
  *   probabilities with thr = 0.5.

@@ -63,6 +63,7 @@ EXPORTS = (
     "uz_confusion_workspace_bytes", "uz_confusion_grid", "uz_confusion_metrics",
     "uz_boundary_workspace_bytes", "uz_boundary_grid", "uz_boundary_loss",
     "uz_lovasz_workspace_bytes", "uz_lovasz_grid", "uz_lovasz_loss",
+    "uz_cldice_workspace_bytes", "uz_cldice_grid", "uz_cldice_loss",
     "uz_postproc_workspace_bytes", "uz_postproc_grid", "uz_postproc",
     "uz_tta_num_views", "uz_flip_views", "uz_tta_merge", "uz_mask_decide",
     "uz_tile_plan", "uz_tile_gather", "uz_tile_blend",
@@ -270,6 +271,23 @@ class LovaszItem(Structure):
 class LovaszDesc(Structure):
     """uz_lovasz_desc"""
     _fields_ = [(n, c_int) for n in ("mode", "n_items", "N", "C", "H", "W", "per_image", "classes", "ignore_index", "main_item")]
+
+
+CLDICE_BINARY, CLDICE_CLASS = 0, 1
+CLDICE_MAX_ITERATIONS = 10       # UZ_CLDICE_MAX_ITERATIONS
+CLDICE_TILE_H, CLDICE_TILE_W = 32, 32      # UZ_CLDICE_TILE_H / _W: the tile of the forward and backward passes
+CLDICE_MAX_ELEMENTS = 1 << 28
+
+
+class ClDiceItem(Structure):
+    """uz_cldice_item: one output map of a uz_cldice_loss call"""
+    _fields_ = [("logits", c_void_p), ("dlogits", c_void_p), ("weight", c_float)]
+
+
+class ClDiceDesc(Structure):
+    """uz_cldice_desc"""
+    _fields_ = [(n, c_int) for n in ("mode", "n_items", "N", "C", "H", "W", "per_image", "include_background", "ignore_index",
+                                     "iterations")] + [("smooth", c_float), ("main_item", c_int)]
 
 
 POST_BINARY, POST_CLASS = 0, 1
@@ -509,6 +527,9 @@ def load():
     lib.uz_lovasz_workspace_bytes.argtypes = [POINTER(LovaszDesc)]
     lib.uz_lovasz_grid.argtypes = [POINTER(LovaszDesc), POINTER(c_int)]
     lib.uz_lovasz_loss.argtypes = [POINTER(LovaszDesc), POINTER(LovaszItem), vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.uz_cldice_workspace_bytes.argtypes = [POINTER(ClDiceDesc)]
+    lib.uz_cldice_grid.argtypes = [POINTER(ClDiceDesc), POINTER(c_int)]
+    lib.uz_cldice_loss.argtypes = [POINTER(ClDiceDesc), POINTER(ClDiceItem), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.uz_postproc_workspace_bytes.argtypes = [POINTER(PostprocDesc)]
     lib.uz_postproc_grid.argtypes = [POINTER(PostprocDesc), POINTER(c_int)]
     lib.uz_postproc.argtypes = [POINTER(PostprocDesc), vp, vp, vp, vp, vp, vp, vp, vp]
@@ -659,6 +680,30 @@ def lovasz_loss(desc: "LovaszDesc", items, target: torch.Tensor, scales: torch.T
     check(load().uz_lovasz_loss(ctypes.byref(desc), items, target.data_ptr(), scales.data_ptr(), base_loss.data_ptr(),
                                 out2.data_ptr(), errors.data_ptr(), ranks.data_ptr(), workspace.data_ptr(), stream_ptr()),
           "uz_lovasz_loss")
+
+
+def cldice_workspace_bytes(desc: "ClDiceDesc") -> int:
+    """uz_cldice_workspace_bytes(): bytes of workspace a uz_cldice_loss call with this descriptor needs"""
+    return check_count(load().uz_cldice_workspace_bytes(ctypes.byref(desc)), "uz_cldice_workspace_bytes")
+
+
+def cldice_grid(desc: "ClDiceDesc") -> tuple:
+    """uz_cldice_grid(): (workgroups, units) of the passes over (map, plane, tile) units of uz_cldice_loss for this descriptor"""
+    units = c_int(0)
+    grid = check_count(load().uz_cldice_grid(ctypes.byref(desc), ctypes.byref(units)), "uz_cldice_grid")
+    return grid, units.value
+
+
+def cldice_loss(desc: "ClDiceDesc", items, target: torch.Tensor, scales: torch.Tensor, base_loss: torch.Tensor,
+                out2: torch.Tensor, probs: torch.Tensor, skeleton: torch.Tensor, target_skeleton: torch.Tensor,
+                workspace: torch.Tensor) -> None:
+    """uz_cldice_loss() on the current stream: `items` is a ctypes array of ClDiceItem (a HOST table, copied into the kernel
+    arguments), scales the (weight, base_scale) pair and base_loss the base criterion's value ON THE DEVICE, out2 a 2-element
+    fp32 device tensor (loss, V of the main map), probs / skeleton the (N, C, H, W) fp32 planes of the main map and
+    target_skeleton the target's.  4 or 6 launches, no allocation, no host read.  Every call of the loss goes through here."""
+    check(load().uz_cldice_loss(ctypes.byref(desc), items, target.data_ptr(), scales.data_ptr(), base_loss.data_ptr(),
+                                out2.data_ptr(), probs.data_ptr(), skeleton.data_ptr(), target_skeleton.data_ptr(),
+                                workspace.data_ptr(), stream_ptr()), "uz_cldice_loss")
 
 
 def postproc_workspace_bytes(desc: "PostprocDesc") -> int:

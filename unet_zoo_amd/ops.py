@@ -1845,6 +1845,37 @@ def lovasz_loss(desc: "L.LovaszDesc", items, target: torch.Tensor, scales: torch
         L.lovasz_loss(desc, items, target, scales, base_loss, out2, errors, ranks, workspace)
 
 
+# ---- ClDiceLoss: soft-skeleton centreline Dice, the skeleton rounds of a tile held in LDS (uz_cldice_loss.hip) ----------------
+def cldice_grid(desc: "L.ClDiceDesc") -> tuple:
+    """(workgroups, units) of the passes over (map, plane, tile) units of uz_cldice_loss for this descriptor: units > workgroups
+    means workgroups walk"""
+    return L.cldice_grid(desc)
+
+
+def cldice_loss(desc: "L.ClDiceDesc", items, target: torch.Tensor, scales: torch.Tensor, base_loss: torch.Tensor,
+                out2: torch.Tensor, probs: torch.Tensor, skeleton: torch.Tensor, target_skeleton: torch.Tensor,
+                workspace: torch.Tensor) -> None:
+    """out2 = (base_scale * base_loss + weight * sum_m ow_m V_m, V_main), probs / skeleton of the main map and target_skeleton
+    (all (N, C, H, W) fp32) <- the maps of `items` (fp32, (N, C, H, W)) against target: fp32 (N, C, H, W) masks
+    (UZ_CLDICE_BINARY) or int32 (N, H, W) labels (UZ_CLDICE_CLASS); the gradient buffers of `items` are rewritten in place;
+    4 or 6 launches"""
+    L.require_cuda(target, scales, base_loss, out2, probs, skeleton, target_skeleton, workspace)
+    for t in (target, scales, base_loss, out2, probs, skeleton, target_skeleton, workspace):
+        assert t.is_contiguous()
+    cls = desc.mode == L.CLDICE_CLASS
+    shape = (desc.N, desc.C, desc.H, desc.W)
+    assert scales.dtype == base_loss.dtype == out2.dtype == probs.dtype == skeleton.dtype == target_skeleton.dtype == torch.float32
+    assert target.dtype == (torch.int32 if cls else torch.float32)
+    assert tuple(target.shape) == ((desc.N, desc.H, desc.W) if cls else shape)
+    assert scales.numel() == 2 and out2.numel() == 2 and base_loss.numel() == 1
+    assert tuple(probs.shape) == tuple(skeleton.shape) == tuple(target_skeleton.shape) == shape
+    elems = desc.n_items * desc.N * desc.C * desc.H * desc.W
+    # per element of every map: logits 4, p written 4 and read by forward, backward and grad 12, dV/dp written and read 8,
+    # the gradient read and written 8 = 36 bytes (the tiles' halos come from L2); the target and its skeleton about 16
+    with _Timed("cldice_loss", 0.0, 16.0 * target.numel() + 36.0 * elems):
+        L.cldice_loss(desc, items, target, scales, base_loss, out2, probs, skeleton, target_skeleton, workspace)
+
+
 # ---- MaskPostprocess / GraphedPredict: components, hole filling, flip TTA (uz_postproc.hip, uz_tta.hip) -----------------------
 def postproc_grid(desc: "L.PostprocDesc") -> tuple:
     """(workgroups, units) of the per-unit launches of uz_postproc for this descriptor: units > workgroups means workgroups
