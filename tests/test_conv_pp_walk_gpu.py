@@ -45,8 +45,8 @@ Not reachable through the ABI:
     Without a reserve cap = 256 / tiles_n >= ntiles: it walks only while a reserve is set.  Its cases ask for two trips.
   * the split-K form launches grid = (ntiles, tiles_n, ksplit): one tile per workgroup, it never walks
     (tests/test_conv_pp_gpu.py keeps it).
-The remaining gap: the second-generation kernels of uz_conv3x3.hip (direct, resident, res64) have a tile loop of their own and
-no test of this kind."""
+The second-generation kernels of uz_conv3x3.hip (direct, resident, res64) have a tile loop of their own: their test of this
+kind is tests/test_conv_direct_walk_gpu.py."""
 from ctypes import byref
 
 import pytest

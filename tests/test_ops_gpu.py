@@ -274,20 +274,38 @@ def test_outconv_fwd_bwd(dt, K):
     assert relerr(db.cpu(), b.grad) < 1e-4
 
 
+# the kernel each case of the test below really runs on the whole chip (uz_conv_igemm_kernel_name): uz_direct_plan keeps
+# Cin == 64 && Nout <= 64 on the LDS-resident direct kernel, and the ping-pong plan takes Nout >= 128 on maps from 8 x 32 up
+RES64_TEST_KERNEL = {
+    (2, 16, 64, 64, 64, 0, False): "conv3x3_direct_bf16_bn64_resident",
+    (1, 50, 70, 64, 64, 0, False): "conv3x3_direct_bf16_bn64_resident",
+    (3, 9, 40, 32, 64, 0, False): "conv3x3_res64_bf16",
+    (2, 24, 33, 16, 32, 0, False): "conv3x3_res64_bf16",
+    (1, 32, 32, 64, 128, 0, False): "conv3x3_pp128w16_bf16",
+    (2, 12, 20, 64, 64, 0, False): "conv3x3_direct_bf16_bn64_resident",
+    (1, 20, 36, 64, 192, 64, False): "conv3x3_pp128w16_bf16",
+    (2, 16, 48, 64, 64, 0, True): "conv3x3_direct_bf16_bn64_resident_up2",
+    (32, 32, 32, 64, 64, 0, False): "conv3x3_direct_bf16_bn64_resident",
+}
+
+
 @pytest.mark.parametrize("N,H,W,Cin,Cout,win,ups", [
-    (2, 16, 64, 64, 64, 0, False),      # the DoubleConv 64 -> 64 layer, several tiles per workgroup column
-    (1, 50, 70, 64, 64, 0, False),      # ragged in both directions
-    (3, 9, 40, 32, 64, 0, False),       # half a K slab (zero-filled by the descriptor range check)
-    (2, 24, 33, 16, 32, 0, False),      # Cin 16, Nout 32: tails on both sides
-    (1, 32, 32, 64, 128, 0, False),     # two workgroup columns of 64 output channels
-    (2, 12, 20, 64, 64, 0, False),      # W < 32: 16x16 patches
-    (1, 20, 36, 64, 192, 64, False),    # input is a channel window of a wider (NaN-poisoned) buffer
-    (2, 16, 48, 64, 64, 0, True),       # nearest x2 upsampled input (UpConvBlock)
-    (32, 32, 32, 64, 64, 0, False),     # more tiles than one wave of workgroups: the deferred epilogue of waves 4-7
+    (2, 16, 64, 64, 64, 0, False),      # the DoubleConv 64 -> 64 layer: the resident direct kernel, 8 tiles on 8 workgroups
+    (1, 50, 70, 64, 64, 0, False),      # ragged in both directions (resident direct kernel)
+    (3, 9, 40, 32, 64, 0, False),       # res64: half a K slab (zero-filled by the descriptor range check)
+    (2, 24, 33, 16, 32, 0, False),      # res64: Cin 16, Nout 32: tails on both sides
+    (1, 32, 32, 64, 128, 0, False),     # two N tiles' worth of output channels: the ping-pong kernel (pp128w16) takes it
+    (2, 12, 20, 64, 64, 0, False),      # W < 32: 16x16 patches (resident direct kernel)
+    (1, 20, 36, 64, 192, 64, False),    # input is a channel window of a wider (NaN-poisoned) buffer (ping-pong kernel, pp128w16)
+    (2, 16, 48, 64, 64, 0, True),       # nearest x2 upsampled input (UpConvBlock; resident direct kernel)
+    (32, 32, 32, 64, 64, 0, False),     # 128 tiles on 128 workgroups of the resident direct kernel: one trip each, no walk
 ])
 def test_conv3x3_res64_register_resident_weights(N, H, W, Cin, Cout, win, ups):
-    """bf16, Cin <= 64: conv3x3_res64_kernel (weights in registers, wave-local epilogue, waves 4-7 half a tile
-    behind) against F.conv2d on the same rounded operands, with bias and the BatchNorm partial sums"""
+    """bf16, Cin <= 64, against F.conv2d on the same rounded operands, with bias and the BatchNorm partial sums.  Written for
+    conv3x3_res64_kernel (weights in registers, wave-local epilogue, waves 4-7 half a tile behind), which only the two cases
+    with Cin < 64 run: uz_direct_plan keeps 64 -> 64 on the LDS-resident direct kernel and the ping-pong plan takes the two
+    cases with Nout >= 128 (RES64_TEST_KERNEL, asserted).  No case makes a second trip through a tile loop; where workgroups
+    of res64 and of the direct kernel walk: tests/test_conv_direct_walk_gpu.py"""
     dt = torch.bfloat16
     g = torch.Generator().manual_seed(5)
     Hi, Wi = (H // 2, W // 2) if ups else (H, W)
@@ -304,6 +322,9 @@ def test_conv3x3_res64_register_resident_weights(N, H, W, Cin, Cout, win, ups):
     wp = ops.pack_weights(w.to(DEV), L.PACK_CONV_FWD, dt)
     y = ops.new_act(N, H, W, Cout, dt, DEV)
     y.buf.fill_(float("nan"))
+    d = L.ConvDesc(L.UZ_BF16, N, H, W, Hi, Wi, Cin, xa.ld, Cout, y.ld, 9, L.TAPS_CONV_UP2 if ups else L.TAPS_CONV, 1,
+                   L.STORE_PLAIN, 0, 0, 0)
+    assert ops.conv_kernel_name(d, with_workspace=True) == RES64_TEST_KERNEL[(N, H, W, Cin, Cout, win, ups)]
     stats = ops.conv_igemm(xa, wp, b.to(DEV), y, ntaps=9, want_stats=True,
                            taps_mode=L.TAPS_CONV_UP2 if ups else L.TAPS_CONV)
     got = y.dense().cpu()
