@@ -460,6 +460,24 @@ int uz_outconv_bwd_bnred(int dtype, const void* x, int ldx, int N, int HW, int C
                          const void* bn_y, int ld_bny, const float* scale, const float* shift, const float* mean,
                          const float* invstd, float* bn_partial, void* stream);
 
+/* The wide 1x1 head (uz_head_wide.hip): the same three products for K = 1..32 classes as a skinny matrix product on the
+ * fp32-input MFMA -- exact fp32 products, fp32 accumulation for bf16 and fp32 activations alike (bf16 is widened in registers;
+ * w and g are never rounded), i.e. the arithmetic class of uz_outconv_* in another order of additions.
+ *   x: NHWC, P = N * HW pixels, C channels, row stride ldx >= C, 16-byte aligned rows;  w: (K, C) fp32;  b: (K) fp32;
+ *   out, g: (N, K, HW) fp32 planes;  dx: T with row stride lddx, NULL = not wanted;  dw: (K, C);  db: (K).
+ * uz_head_wide_supported: 1 for bf16 / fp32, C % VEC == 0 (8 / 4), C <= 512, 1 <= K <= 32.
+ * uz_head_wide_grid: the workgroups of the forward's walk over 256-pixel tiles.  It is sized from the hardware's CU count,
+ * never from uz_set_cu_reserve(), and so is the backward's (workspace bytes / (4 K (C + 1)) partial rows): the order of the
+ * additions is a function of the shape alone, the results are bit-identical from call to call (no atomics).
+ * UZ_EINVAL with a message before any launch: N * HW >= 2^31, a null required pointer, ldx < C, K or C out of range. */
+int uz_head_wide_supported(int dtype, int C, int K);
+int uz_head_wide_grid(int dtype, int N, int HW, int C, int K);
+int uz_head_wide_fwd(int dtype, const void* x, int ldx, int N, int HW, int C, const float* w, const float* b, int K,
+                     float* out, void* stream);
+long long uz_head_wide_bwd_workspace_bytes(int dtype, int N, int HW, int C, int K);
+int uz_head_wide_bwd(int dtype, const void* x, int ldx, int N, int HW, int C, const float* w, int K, const float* g,
+                     void* dx, int lddx, float* dw, float* db, void* workspace, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Additive attention gate (AttentionBlock.forward, attention_unet.py:34-40), everything except the
  * two 1x1 convolutions W_g / W_x (those are uz_conv_igemm with statistics):

@@ -2028,6 +2028,8 @@ class Engine:
         K = conv.out_channels
         w = conv.weight.detach().reshape(K, x.C)
         b = conv.bias.detach() if conv.bias is not None else torch.zeros(K, device=self.device)
+        if K > ops.HEAD_NARROW_MAX_K:
+            return self._out_conv_wide(x, conv, w, b)
         assert x.lazy is None or sole_reader, "a lazy activation goes to the head it was deferred for"
         xf = x.take_lazy()      # x is the raw output of a convolution (conv_bn_relu(defer_apply=this head))
         logits = ops.outconv_fwd(x, w, b, xform=xf)
@@ -2055,6 +2057,34 @@ class Engine:
                 if virt:
                     x.add_grad(ops.HeadGrad(gl, w, part))
                 elif dx is not None:
+                    x.add_grad(dx)
+
+            self._heads.append((bwd, 1))
+        return logits
+
+    def _out_conv_wide(self, x: Act, conv: nn.Conv2d, w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+        """out_conv for 9..32 classes (uz_head_wide_*): the plain form only.  The narrow head's three other forms -- the
+        BatchNorm first pass in its backward (bnred), the lazy input and the virtual head gradient -- keep the classes of a
+        lane in registers and end at 8; _defer_to_head declines through outconv_xform_supported, so x is a real tensor here
+        whatever sole_reader says, and the producing block runs its own BatchNorm backward passes."""
+        K = conv.out_channels
+        assert x.lazy is None, "no head with more than 8 classes reads a lazy activation (_defer_to_head declines it)"
+        if not ops.head_wide_supported(x, K):
+            raise ValueError(f"out_conv: no kernel takes a 1x1 head of {K} classes on {x.C} channels ({x.dtype}, row stride {x.ld}): "
+                             f"the wide head takes 9..{ops.HEAD_WIDE_MAX_K} classes, at most 512 channels in whole 16-byte vectors")
+        w, b = w.float().contiguous(), b.float().contiguous()
+        logits = ops.head_wide_fwd(x, w, b)
+        if self.record:
+            def bwd(g_logits: torch.Tensor):
+                dwt = self._dst(conv.weight)
+                dbt = self._dst(conv.bias) if conv.bias is not None else None
+                dx = self.new_act(x.N, x.H, x.W, x.C) if x.needs_grad else None
+                dw, db = ops.head_wide_bwd(x, w, g_logits.contiguous().float(), dx,
+                                           dwt.view(K, x.C) if dwt is not None else None, dbt)
+                self._give_grad(conv.weight, dwt if dwt is not None else dw.reshape(conv.weight.shape))
+                if conv.bias is not None:
+                    self._give_grad(conv.bias, db)
+                if dx is not None:
                     x.add_grad(dx)
 
             self._heads.append((bwd, 1))

@@ -819,6 +819,58 @@ def outconv_bwd(x: Act, w: torch.Tensor, g: torch.Tensor, dx: Optional[Act],
     return dw.view(K, x.C), db
 
 
+HEAD_NARROW_MAX_K = 8     # uz_outconv_*: the classes of a lane stay in registers
+HEAD_WIDE_MAX_K = 32      # uz_head_wide_*: the classes are the accumulator tile of the fp32 MFMA; = CLASS_MAX_K of the criteria
+
+
+def head_wide_supported(x: Act, K: int) -> bool:
+    """uz_head_wide_* take this activation: bf16 / fp32, C a multiple of the 16-byte vector, C <= 512, 1 <= K <= 32"""
+    if x.dtype not in (torch.bfloat16, torch.float32):
+        return False
+    vec = 8 if x.dtype == torch.bfloat16 else 4
+    return bool(L.load().uz_head_wide_supported(L.dtype_code(x.dtype), x.C, K)) and x.ld % vec == 0
+
+
+def head_wide_fwd(x: Act, w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """logits (N, K, H, W) fp32 of a 1x1 head with up to 32 classes: exact fp32 products on the fp32-input MFMA"""
+    lib = L.load()
+    K = w.shape[0]
+    assert w.dtype == torch.float32 and w.is_contiguous() and w.shape == (K, x.C)
+    assert b.dtype == torch.float32 and b.is_contiguous() and b.shape == (K,)
+    out = torch.empty((x.N, K, x.H, x.W), dtype=torch.float32, device=x.buf.device)
+    es = x.buf.element_size()
+    with _Timed("head_wide_fwd", 2.0 * K * x.P * x.C, es * x.P * x.C + 4.0 * K * x.P):
+        L.check(lib.uz_head_wide_fwd(L.dtype_code(x.dtype), x.ptr(), x.ld, x.N, x.H * x.W, x.C, w.data_ptr(), b.data_ptr(), K,
+                                     out.data_ptr(), L.stream_ptr()), "uz_head_wide_fwd")
+    return out
+
+
+def head_wide_bwd(x: Act, w: torch.Tensor, g: torch.Tensor, dx: Optional[Act],
+                  dw: Optional[torch.Tensor] = None, db: Optional[torch.Tensor] = None):
+    """(dw (K, C), db (K)) of the wide head, and its input gradient into dx when one is given; partial rows per workgroup and
+    a fixed-order sum: bit-identical from call to call"""
+    lib = L.load()
+    K = w.shape[0]
+    assert g.dtype == torch.float32 and g.is_contiguous() and g.shape == (x.N, K, x.H, x.W)
+    assert w.dtype == torch.float32 and w.is_contiguous() and w.shape == (K, x.C)
+    assert dx is None or (dx.dtype == x.dtype and (dx.P, dx.C) == (x.P, x.C))
+    dev = x.buf.device
+    if dw is None:
+        dw = torch.empty((K, x.C), dtype=torch.float32, device=dev)
+    if db is None:
+        db = torch.empty(K, dtype=torch.float32, device=dev)
+    code = L.dtype_code(x.dtype)
+    wsb = L.check_count(lib.uz_head_wide_bwd_workspace_bytes(code, x.N, x.H * x.W, x.C, K), "uz_head_wide_bwd_workspace_bytes")
+    ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev)
+    es = x.buf.element_size()
+    with _Timed("head_wide_bwd", (4.0 if dx is not None else 2.0) * K * x.P * x.C,
+                es * x.P * x.C * (2 if dx is not None else 1) + 4.0 * K * x.P):
+        L.check(lib.uz_head_wide_bwd(code, x.ptr(), x.ld, x.N, x.H * x.W, x.C, w.data_ptr(), K, g.data_ptr(),
+                                     dx.ptr() if dx is not None else None, dx.ld if dx is not None else 0,
+                                     dw.data_ptr(), db.data_ptr(), ws.data_ptr(), L.stream_ptr()), "uz_head_wide_bwd")
+    return dw.view(K, x.C), db
+
+
 def colsum(x: Act, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """per-channel sums over the pixels / tokens (fp32), deterministic two-stage reduction"""
     lib = L.load()
