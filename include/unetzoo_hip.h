@@ -874,11 +874,14 @@ int uz_region_loss(const uz_region_desc* d, const uz_region_item* items, float* 
 #define UZ_CLASS_MAX_K 32
 #define UZ_CLASS_REDUCE_BATCH 0
 #define UZ_CLASS_REDUCE_IMAGE 1
-typedef struct uz_class_item {
+/* one output map of a composed loss (uz_class_loss, uz_boundary_loss, uz_lovasz_loss, uz_cldice_loss): the four item
+ * names are one type */
+typedef struct uz_map_item {
   const float* logits;
-  float* dlogits; /* nullable */
+  float* dlogits; /* nullable; in: the base loss's gradient where there is one, out: the combined one */
   float weight;
-} uz_class_item;
+} uz_map_item;
+typedef uz_map_item uz_class_item;
 typedef struct uz_class_desc {
   int n_items;
   int N, K;
@@ -1310,11 +1313,7 @@ int uz_confusion_metrics(const uz_confusion_desc* d, const float* logits, const 
  * overlapping any other buffer of the call. */
 #define UZ_BOUNDARY_BINARY 0
 #define UZ_BOUNDARY_CLASS 1
-typedef struct uz_boundary_item {
-  const float* logits;
-  float* dlogits; /* nullable; in: the base loss's gradient, out: the combined one */
-  float weight;
-} uz_boundary_item;
+typedef uz_map_item uz_boundary_item;
 typedef struct uz_boundary_desc {
   int mode; /* UZ_BOUNDARY_* */
   int n_items;
@@ -1372,11 +1371,7 @@ int uz_boundary_loss(const uz_boundary_desc* d, const uz_boundary_item* items, c
 #define UZ_LOVASZ_CLASS 1
 #define UZ_LOVASZ_PRESENT 0
 #define UZ_LOVASZ_ALL 1
-typedef struct uz_lovasz_item {
-  const float* logits;
-  float* dlogits; /* nullable; in: the base loss's gradient, out: the combined one */
-  float weight;
-} uz_lovasz_item;
+typedef uz_map_item uz_lovasz_item;
 typedef struct uz_lovasz_desc {
   int mode; /* UZ_LOVASZ_BINARY / UZ_LOVASZ_CLASS */
   int n_items;
@@ -1432,11 +1427,7 @@ int uz_lovasz_loss(const uz_lovasz_desc* d, const uz_lovasz_item* items, const v
 #define UZ_CLDICE_MAX_ITERATIONS 10
 #define UZ_CLDICE_TILE_H 32
 #define UZ_CLDICE_TILE_W 32
-typedef struct uz_cldice_item {
-  const float* logits;
-  float* dlogits; /* nullable; in: the base loss's gradient, out: the combined one */
-  float weight;
-} uz_cldice_item;
+typedef uz_map_item uz_cldice_item;
 typedef struct uz_cldice_desc {
   int mode; /* UZ_CLDICE_BINARY / UZ_CLDICE_CLASS */
   int n_items;

@@ -91,17 +91,18 @@ def test_bad_descriptor_is_rejected_without_a_gpu():
 
 def test_library_is_the_build_of_the_sources_in_the_tree():
     """libunetzoo_hip.so is a build artefact (git-ignored; it travels to the GPU box as it is): uz_source_hash() must be
-    the sha256 of the kernel sources as they are in the tree now, in the Makefile's order -- a stale library would
-    otherwise be tested and timed in place of the code under review (it happened in round 3: a reverted experiment
-    stayed in the .so for a dozen measurements)"""
+    the sha256 of the kernel sources as they are in the tree now, in the Makefile's order ($(SRCS), every internal header
+    of csrc in sorted order, the public header) -- a stale library would otherwise be tested and timed in place of the
+    code under review (it happened in round 3: a reverted experiment stayed in the .so for a dozen measurements)"""
     import hashlib
     import re
     from unet_zoo_amd import _lib as L
     csrc = os.path.join(ROOT, "unet_zoo_amd", "csrc")
     mk = open(os.path.join(csrc, "Makefile")).read()
     srcs = re.search(r"^SRCS = (.*)$", mk, re.M).group(1).split()
-    files = [os.path.join(csrc, f) for f in srcs] + [os.path.join(csrc, "uz_common.h"),
-                                                      os.path.join(ROOT, "include", "unetzoo_hip.h")]
+    hdrs = sorted(f for f in os.listdir(csrc) if f.endswith(".h"))      # $(sort $(wildcard *.h)): a new header is hashed too
+    assert "uz_host.h" in hdrs and "uz_postproc_core.h" in hdrs
+    files = [os.path.join(csrc, f) for f in srcs + hdrs] + [os.path.join(ROOT, "include", "unetzoo_hip.h")]
     h = hashlib.sha256()
     for f in files:
         h.update(open(f, "rb").read())

@@ -235,3 +235,43 @@ def test_the_library_refuses_before_any_launch():
     assert units == 16 * 256 and grid < units                                   # workgroups walk
     for shape in ((16, 1, 256, 256), (16, 8, 256, 256), (8, 1, 512, 512)):      # the shapes of tools/cldice_bench.py
         assert L.cldice_workspace_bytes(_desc(n_items=7 if shape[0] == 8 else 1, N=shape[0], C=shape[1], H=shape[2], W=shape[3])) > 0
+
+
+def test_null_and_overlapping_pointers_are_refused_before_any_launch():
+    import ctypes
+    lib = L.load()
+    assert lib.uz_cldice_workspace_bytes(None) == -1 and b"null descriptor" in lib.uz_last_error_string()
+    assert lib.uz_cldice_grid(None, None) < 0 and b"null descriptor" in lib.uz_last_error_string()
+    d = _desc(N=2)                                                    # 2 x 1 x 8 x 8: maps of 512 bytes
+    assert 16 <= L.cldice_workspace_bytes(d) < 0x10000
+    items = (L.ClDiceItem * 1)()
+    items[0].logits, items[0].dlogits, items[0].weight = 0x10000, 0x20000, 1.0
+    # the other pointers at disjoint made-up addresses: nothing is dereferenced before the checks
+    ok = dict(target=0x30000, scales=0x40000, base_loss=0x40100, out=0x40200, probs=0x50000, skeleton=0x58000, tskel=0x60000, ws=0x100000)
+
+    def call(its=items, **kw):
+        a = dict(ok)
+        a.update(kw)
+        return lib.uz_cldice_loss(ctypes.byref(d), its, a["target"], a["scales"], a["base_loss"], a["out"], a["probs"], a["skeleton"],
+                                  a["tskel"], a["ws"], None)
+
+    def item(logits, dlogits, weight):
+        its = (L.ClDiceItem * 1)()
+        its[0].logits, its[0].dlogits, its[0].weight = logits, dlogits, weight
+        return its
+
+    for name in ok:
+        assert call(**{name: None}) < 0 and b"uz_cldice_loss: null pointer" in lib.uz_last_error_string(), name
+    assert lib.uz_cldice_loss(ctypes.byref(d), None, *ok.values(), None) < 0 and b"null pointer" in lib.uz_last_error_string()
+    assert call(its=item(None, 0x20000, 1.0)) < 0 and b"uz_cldice_loss: item 0 has null logits" in lib.uz_last_error_string()
+    assert call(its=item(0x10000, None, -1.0)) < 0 and b"uz_cldice_loss: item 0 has a negative weight" in lib.uz_last_error_string()
+    assert call(ws=0x100008) < 0 and b"uz_cldice_loss: the workspace must be 16-byte aligned" in lib.uz_last_error_string()
+    for kw in (dict(probs=0x50002), dict(skeleton=0x58002), dict(tskel=0x60002), dict(out=0x40202), dict(its=item(0x10000, 0x20002, 1.0)),
+               dict(its=item(0x10002, 0x20000, 1.0))):
+        assert call(**kw) < 0 and b"uz_cldice_loss: tensors must be 4-byte aligned" in lib.uz_last_error_string(), kw
+    for kw in (dict(out=0x40000 + 4), dict(out=0x40100), dict(probs=0x30000 + 256), dict(skeleton=0x10000), dict(tskel=0x30000 - 64),
+               dict(ws=0x30000 - 16), dict(its=item(0x10000, 0x30000 + 128, 1.0)),           # every output over an input
+               dict(out=0x50000), dict(probs=0x58000 + 4), dict(skeleton=0x60000 - 4), dict(tskel=0x100000 + 16), dict(ws=0x20000 - 16),
+               dict(its=item(0x10000, 0x50000 + 64, 1.0)), dict(its=item(0x10000, 0x60000 + 64, 1.0)),      # every output over another
+               dict(its=item(0x10000, 0x10000 + 64, 1.0))):                                  # dlogits inside logits
+        assert call(**kw) < 0 and b"uz_cldice_loss: tensors overlap" in lib.uz_last_error_string(), kw

@@ -176,9 +176,13 @@ CLASS_MAX_K = 32
 CLASS_REDUCE_BATCH, CLASS_REDUCE_IMAGE = 0, 1
 
 
-class ClassItem(Structure):
-    """uz_class_item: one output map of a uz_class_loss call"""
+class MapItem(Structure):
+    """uz_map_item: one output map of a composed loss call; uz_class_item, uz_boundary_item, uz_lovasz_item and
+    uz_cldice_item are this one type"""
     _fields_ = [("logits", c_void_p), ("dlogits", c_void_p), ("weight", c_float)]
+
+
+ClassItem = BoundaryItem = LovaszItem = ClDiceItem = MapItem
 
 
 class ClassDesc(Structure):
@@ -234,11 +238,6 @@ BOUNDARY_BINARY, BOUNDARY_CLASS = 0, 1
 BOUNDARY_MAX_HW = 4096
 
 
-class BoundaryItem(Structure):
-    """uz_boundary_item: one output map of a uz_boundary_loss call"""
-    _fields_ = [("logits", c_void_p), ("dlogits", c_void_p), ("weight", c_float)]
-
-
 class BoundaryDesc(Structure):
     """uz_boundary_desc"""
     _fields_ = [(n, c_int) for n in ("mode", "n_items", "N", "C", "H", "W", "first_class", "ignore_index", "metric_item")] \
@@ -264,11 +263,6 @@ LOVASZ_MAX_SEGMENT = 1 << 22
 LOVASZ_MAX_ELEMENTS = 1 << 28
 
 
-class LovaszItem(Structure):
-    """uz_lovasz_item: one output map of a uz_lovasz_loss call"""
-    _fields_ = [("logits", c_void_p), ("dlogits", c_void_p), ("weight", c_float)]
-
-
 class LovaszDesc(Structure):
     """uz_lovasz_desc"""
     _fields_ = [(n, c_int) for n in ("mode", "n_items", "N", "C", "H", "W", "per_image", "classes", "ignore_index", "main_item")]
@@ -278,11 +272,6 @@ CLDICE_BINARY, CLDICE_CLASS = 0, 1
 CLDICE_MAX_ITERATIONS = 10       # UZ_CLDICE_MAX_ITERATIONS
 CLDICE_TILE_H, CLDICE_TILE_W = 32, 32      # UZ_CLDICE_TILE_H / _W: the tile of the forward and backward passes
 CLDICE_MAX_ELEMENTS = 1 << 28
-
-
-class ClDiceItem(Structure):
-    """uz_cldice_item: one output map of a uz_cldice_loss call"""
-    _fields_ = [("logits", c_void_p), ("dlogits", c_void_p), ("weight", c_float)]
 
 
 class ClDiceDesc(Structure):
@@ -574,9 +563,21 @@ def check_count(rc: int, what: str) -> int:
     return rc
 
 
+def _desc_bytes(name: str, desc) -> int:
+    """A byte count of a descriptor (uz_X_workspace_bytes, uz_patch_index_bytes): negative is the library's refusal."""
+    return check_count(getattr(load(), name)(ctypes.byref(desc)), name)
+
+
+def _desc_grid(name: str, desc) -> tuple:
+    """(workgroups, units) of a descriptor (uz_X_grid): units > workgroups means workgroups walk."""
+    units = c_int(0)
+    grid = check_count(getattr(load(), name)(ctypes.byref(desc), ctypes.byref(units)), name)
+    return grid, units.value
+
+
 def region_loss_workspace_bytes(desc: "RegionDesc") -> int:
     """uz_region_loss_workspace_bytes(): bytes of workspace a uz_region_loss call with this descriptor needs"""
-    return check_count(load().uz_region_loss_workspace_bytes(ctypes.byref(desc)), "uz_region_loss_workspace_bytes")
+    return _desc_bytes("uz_region_loss_workspace_bytes", desc)
 
 
 def region_loss(desc: "RegionDesc", items, out2: torch.Tensor, workspace: torch.Tensor) -> None:
@@ -588,7 +589,7 @@ def region_loss(desc: "RegionDesc", items, out2: torch.Tensor, workspace: torch.
 
 def class_loss_workspace_bytes(desc: "ClassDesc") -> int:
     """uz_class_loss_workspace_bytes(): bytes of workspace a uz_class_loss call with this descriptor needs"""
-    return check_count(load().uz_class_loss_workspace_bytes(ctypes.byref(desc)), "uz_class_loss_workspace_bytes")
+    return _desc_bytes("uz_class_loss_workspace_bytes", desc)
 
 
 def class_loss(desc: "ClassDesc", items, labels: torch.Tensor, class_weight, out2: torch.Tensor, counts: torch.Tensor,
@@ -604,14 +605,12 @@ def class_loss(desc: "ClassDesc", items, labels: torch.Tensor, class_weight, out
 
 def surface_workspace_bytes(desc: "SurfaceDesc") -> int:
     """uz_surface_workspace_bytes(): bytes of workspace a uz_surface_metrics call with this descriptor needs"""
-    return check_count(load().uz_surface_workspace_bytes(ctypes.byref(desc)), "uz_surface_workspace_bytes")
+    return _desc_bytes("uz_surface_workspace_bytes", desc)
 
 
 def surface_grid(desc: "SurfaceDesc") -> tuple:
     """uz_surface_grid(): (workgroups, units) of the widest launch of uz_surface_metrics for this descriptor"""
-    units = c_int(0)
-    grid = check_count(load().uz_surface_grid(ctypes.byref(desc), ctypes.byref(units)), "uz_surface_grid")
-    return grid, units.value
+    return _desc_grid("uz_surface_grid", desc)
 
 
 def surface_metrics(desc: "SurfaceDesc", logits: torch.Tensor, target: torch.Tensor, out: torch.Tensor, stats: torch.Tensor,
@@ -623,14 +622,12 @@ def surface_metrics(desc: "SurfaceDesc", logits: torch.Tensor, target: torch.Ten
 
 def confusion_workspace_bytes(desc: "ConfusionDesc") -> int:
     """uz_confusion_workspace_bytes(): bytes of workspace a uz_confusion_metrics call with this descriptor needs"""
-    return check_count(load().uz_confusion_workspace_bytes(ctypes.byref(desc)), "uz_confusion_workspace_bytes")
+    return _desc_bytes("uz_confusion_workspace_bytes", desc)
 
 
 def confusion_grid(desc: "ConfusionDesc") -> tuple:
     """uz_confusion_grid(): (workgroups, units) of the counting pass of uz_confusion_metrics for this descriptor"""
-    units = c_int(0)
-    grid = check_count(load().uz_confusion_grid(ctypes.byref(desc), ctypes.byref(units)), "uz_confusion_grid")
-    return grid, units.value
+    return _desc_grid("uz_confusion_grid", desc)
 
 
 def confusion_metrics(desc: "ConfusionDesc", logits: torch.Tensor, target: torch.Tensor, edges, counts: torch.Tensor, hist,
@@ -645,14 +642,12 @@ def confusion_metrics(desc: "ConfusionDesc", logits: torch.Tensor, target: torch
 
 def boundary_workspace_bytes(desc: "BoundaryDesc") -> int:
     """uz_boundary_workspace_bytes(): bytes of workspace a uz_boundary_loss call with this descriptor needs"""
-    return check_count(load().uz_boundary_workspace_bytes(ctypes.byref(desc)), "uz_boundary_workspace_bytes")
+    return _desc_bytes("uz_boundary_workspace_bytes", desc)
 
 
 def boundary_grid(desc: "BoundaryDesc") -> tuple:
     """uz_boundary_grid(): (workgroups, units) of the column pass of uz_boundary_loss for this descriptor"""
-    units = c_int(0)
-    grid = check_count(load().uz_boundary_grid(ctypes.byref(desc), ctypes.byref(units)), "uz_boundary_grid")
-    return grid, units.value
+    return _desc_grid("uz_boundary_grid", desc)
 
 
 def boundary_loss(desc: "BoundaryDesc", items, target: torch.Tensor, scales: torch.Tensor, base_loss: torch.Tensor,
@@ -667,14 +662,12 @@ def boundary_loss(desc: "BoundaryDesc", items, target: torch.Tensor, scales: tor
 
 def lovasz_workspace_bytes(desc: "LovaszDesc") -> int:
     """uz_lovasz_workspace_bytes(): bytes of workspace a uz_lovasz_loss call with this descriptor needs"""
-    return check_count(load().uz_lovasz_workspace_bytes(ctypes.byref(desc)), "uz_lovasz_workspace_bytes")
+    return _desc_bytes("uz_lovasz_workspace_bytes", desc)
 
 
 def lovasz_grid(desc: "LovaszDesc") -> tuple:
     """uz_lovasz_grid(): (workgroups, units) of the passes over (segment, tile) units of uz_lovasz_loss for this descriptor"""
-    units = c_int(0)
-    grid = check_count(load().uz_lovasz_grid(ctypes.byref(desc), ctypes.byref(units)), "uz_lovasz_grid")
-    return grid, units.value
+    return _desc_grid("uz_lovasz_grid", desc)
 
 
 def lovasz_loss(desc: "LovaszDesc", items, target: torch.Tensor, scales: torch.Tensor, base_loss: torch.Tensor,
@@ -690,14 +683,12 @@ def lovasz_loss(desc: "LovaszDesc", items, target: torch.Tensor, scales: torch.T
 
 def cldice_workspace_bytes(desc: "ClDiceDesc") -> int:
     """uz_cldice_workspace_bytes(): bytes of workspace a uz_cldice_loss call with this descriptor needs"""
-    return check_count(load().uz_cldice_workspace_bytes(ctypes.byref(desc)), "uz_cldice_workspace_bytes")
+    return _desc_bytes("uz_cldice_workspace_bytes", desc)
 
 
 def cldice_grid(desc: "ClDiceDesc") -> tuple:
     """uz_cldice_grid(): (workgroups, units) of the passes over (map, plane, tile) units of uz_cldice_loss for this descriptor"""
-    units = c_int(0)
-    grid = check_count(load().uz_cldice_grid(ctypes.byref(desc), ctypes.byref(units)), "uz_cldice_grid")
-    return grid, units.value
+    return _desc_grid("uz_cldice_grid", desc)
 
 
 def cldice_loss(desc: "ClDiceDesc", items, target: torch.Tensor, scales: torch.Tensor, base_loss: torch.Tensor,
@@ -714,14 +705,12 @@ def cldice_loss(desc: "ClDiceDesc", items, target: torch.Tensor, scales: torch.T
 
 def postproc_workspace_bytes(desc: "PostprocDesc") -> int:
     """uz_postproc_workspace_bytes(): bytes of workspace a uz_postproc call with this descriptor needs"""
-    return check_count(load().uz_postproc_workspace_bytes(ctypes.byref(desc)), "uz_postproc_workspace_bytes")
+    return _desc_bytes("uz_postproc_workspace_bytes", desc)
 
 
 def postproc_grid(desc: "PostprocDesc") -> tuple:
     """uz_postproc_grid(): (workgroups, units) of the per-unit launches of uz_postproc for this descriptor"""
-    units = c_int(0)
-    grid = check_count(load().uz_postproc_grid(ctypes.byref(desc), ctypes.byref(units)), "uz_postproc_grid")
-    return grid, units.value
+    return _desc_grid("uz_postproc_grid", desc)
 
 
 def _ptr(t) -> "int | None":

@@ -269,16 +269,9 @@ int aug_plan(const uz_augment_desc* d, const char* who, AugPlan* p) {
   s.gsy = d->G ? (float)((double)(d->G - 1) / (double)(d->H - 1)) : 0.f;
   s.image_fill = d->image_fill, s.mask_fill = d->mask_fill, s.label_fill = d->label_fill;
   // eight workgroups of four waves per CU of the hardware: what can be resident at once; more units than that are walked
-  const int cap = 8 * UZ_NUM_CU_HW;
-  p->grid = s.units < cap ? s.units : cap;
+  p->grid = uz_grid_cap(s.units, 8);
   return UZ_OK;
 }
-
-struct AugRange {
-  uintptr_t lo, hi;
-};
-AugRange aug_range(const void* p, long long bytes) { return {(uintptr_t)p, (uintptr_t)p + (uintptr_t)bytes}; }
-bool aug_overlap(const AugRange& x, const AugRange& y) { return x.lo < y.hi && y.lo < x.hi; }
 
 template <int C>
 void aug_launch(int mk, const AugPlan& p, hipStream_t s, const float* image, const void* mask, const float* params, const float* disp,
@@ -295,7 +288,7 @@ extern "C" int uz_augment_params(const uz_augment_desc* d, const float* u, float
   const int rc = aug_check_ranges(d, "uz_augment_params");
   if (rc != UZ_OK) return rc;
   UZ_REQUIRE(u && params, "uz_augment_params: null pointer");
-  UZ_REQUIRE(!aug_overlap(aug_range(u, 32LL * d->N), aug_range(params, 64LL * d->N)), "uz_augment_params: u and params overlap");
+  UZ_REQUIRE(!uz_overlap(uz_range(u, 32LL * d->N), uz_range(params, 64LL * d->N)), "uz_augment_params: u and params overlap");
   AugRanges r;
   r.p_hflip = d->p_hflip, r.p_vflip = d->p_vflip, r.rotate = d->rotate, r.scale_min = d->scale_min, r.scale_max = d->scale_max;
   r.translate = d->translate, r.brightness = d->brightness, r.contrast = d->contrast;
@@ -324,12 +317,12 @@ extern "C" int uz_augment_apply(const uz_augment_desc* d, const float* image, co
   UZ_REQUIRE((d->G > 0) == (disp != nullptr), "uz_augment_apply: the displacement grid does not match G = %d (null pointer, or a pointer with G = 0)", d->G);
   const long long px = (long long)d->N * d->H * d->W;
   const long long mbytes = d->mask_kind == UZ_AUGMENT_MASK_NONE ? 0 : 4LL * px * p.sh.Cm;
-  const AugRange in[4] = {aug_range(image, 4LL * px * d->C), aug_range(mask, mbytes), aug_range(params, 64LL * d->N),
-                          aug_range(disp, d->G ? 8LL * d->N * d->G * d->G : 0)};
-  const AugRange out[2] = {aug_range(image_out, 4LL * px * d->C), aug_range(mask_out, mbytes)};
-  for (int o = 0; o < 2; ++o)
-    for (int i = 0; i < 4; ++i) UZ_REQUIRE(!aug_overlap(out[o], in[i]), "uz_augment_apply: an output overlaps an input (the warp cannot run in place)");
-  UZ_REQUIRE(!aug_overlap(out[0], out[1]), "uz_augment_apply: the two outputs overlap");
+  const UzRange in[4] = {uz_range(image, 4LL * px * d->C), uz_range(mask, mbytes), uz_range(params, 64LL * d->N),
+                         uz_range(disp, 8LL * d->N * d->G * d->G)};
+  const UzRange out[2] = {uz_range(image_out, 4LL * px * d->C), uz_range(mask_out, mbytes)};
+  UZ_REQUIRE(!uz_any_overlap(&out[0], 1, in, 4) && !uz_any_overlap(&out[1], 1, in, 4),
+             "uz_augment_apply: an output overlaps an input (the warp cannot run in place)");
+  UZ_REQUIRE(!uz_any_overlap(out, 2, nullptr, 0), "uz_augment_apply: the two outputs overlap");
   UZ_REQUIRE(((uintptr_t)image & 3) == 0 && ((uintptr_t)mask & 3) == 0 && ((uintptr_t)params & 3) == 0 && ((uintptr_t)disp & 3) == 0 &&
                  ((uintptr_t)image_out & 3) == 0 && ((uintptr_t)mask_out & 3) == 0,
              "uz_augment_apply: tensors must be 4-byte aligned");

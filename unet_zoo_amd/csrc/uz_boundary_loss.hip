@@ -311,12 +311,10 @@ __global__ __launch_bounds__(BL_THREADS) void boundary_finalize_kernel(const BlI
   }
 }
 
-long long bl_align(long long b) { return (b + 15) / 16 * 16; }
-
 struct BlPlan {
   BlGeo geo;
   int grid;                     // the column pass
-  int loss_grid;
+  int rows_grid, planes_grid, loss_grid;
   long long off[4], bytes;      // g, cnt, part, rowinfo
 };
 
@@ -352,25 +350,14 @@ int bl_plan(const uz_boundary_desc* d, const char* who, BlPlan* p) {
   g.inv_den = (float)(1.0 / ((double)g.M * (double)g.HW));
   g.pixels = cls ? (long long)d->N * g.HW : (long long)g.M * g.HW;
   // eight workgroups of four waves per CU of the hardware: what can be resident at once; more units than that are walked
-  const int cap = 8 * UZ_NUM_CU_HW;
-  p->grid = g.units < cap ? g.units : cap;
-  const long long lb = (g.pixels + BL_THREADS - 1) / BL_THREADS;
-  p->loss_grid = (int)(lb < cap ? lb : cap);
+  p->rows_grid = uz_grid_cap((long long)g.M * g.H, 8);
+  p->planes_grid = uz_grid_cap(g.M, 8);
+  p->grid = uz_grid_cap(g.units, 8);
+  p->loss_grid = uz_grid_cap((g.pixels + BL_THREADS - 1) / BL_THREADS, 8);
   const long long sizes[4] = {2LL * g.M * g.HW, 4LL * g.M * BL_CNT, 8LL * p->loss_grid * g.n_items, 8LL * g.M * g.H};
-  long long at = 0;
-  for (int e = 0; e < 4; ++e) {
-    p->off[e] = at;
-    at += bl_align(sizes[e]);
-  }
-  p->bytes = at;
+  p->bytes = uz_carve(sizes, 4, p->off);
   return UZ_OK;
 }
-
-struct BlRange {
-  uintptr_t lo, hi;
-};
-BlRange bl_range(const void* p, long long bytes) { return {(uintptr_t)p, (uintptr_t)p + (uintptr_t)bytes}; }
-bool bl_overlap(const BlRange& x, const BlRange& y) { return x.lo < y.hi && y.lo < x.hi; }
 
 }  // namespace
 
@@ -400,45 +387,29 @@ extern "C" int uz_boundary_loss(const uz_boundary_desc* d, const uz_boundary_ite
   const BlGeo& g = p.geo;
   const long long map_bytes = 4LL * d->N * d->C * g.HW;
   // what the call writes (out, sd2, workspace, every dlogits) against everything else it touches
-  BlRange in[3 + UZ_CLASS_MAX_ITEMS], outr[3 + UZ_CLASS_MAX_ITEMS];
-  int n_in = 0, n_out = 0;
-  in[n_in++] = bl_range(target, d->mode == UZ_BOUNDARY_CLASS ? 4LL * d->N * g.HW : map_bytes);
-  in[n_in++] = bl_range(scales, 8);
-  in[n_in++] = bl_range(base_loss, 4);
-  outr[n_out++] = bl_range(out, 8);
-  outr[n_out++] = bl_range(sd2, 4LL * g.M * g.HW);
-  outr[n_out++] = bl_range(workspace, p.bytes);
+  UzRange in[3 + UZ_CLASS_MAX_ITEMS] = {uz_range(target, d->mode == UZ_BOUNDARY_CLASS ? 4LL * d->N * g.HW : map_bytes), uz_range(scales, 8),
+                                        uz_range(base_loss, 4)};
+  UzRange outr[3 + UZ_CLASS_MAX_ITEMS] = {uz_range(out, 8), uz_range(sd2, 4LL * g.M * g.HW), uz_range(workspace, p.bytes)};
+  int n_in = 3, n_out = 3;
   BlItems tab;
-  for (int i = 0; i < d->n_items; ++i) {
-    const uz_boundary_item& it = items[i];
-    UZ_REQUIRE(it.logits != nullptr, "uz_boundary_loss: item %d has null logits", i);
-    UZ_REQUIRE((((uintptr_t)it.logits | (uintptr_t)it.dlogits) & 3) == 0, "uz_boundary_loss: tensors must be 4-byte aligned");
-    UZ_REQUIRE(it.weight >= 0.f && it.weight < INFINITY, "uz_boundary_loss: item %d has a negative weight", i);
-    in[n_in++] = bl_range(it.logits, map_bytes);
-    if (it.dlogits != nullptr) outr[n_out++] = bl_range(it.dlogits, map_bytes);
-    tab.it[i] = it;
-  }
-  for (int i = d->n_items; i < UZ_CLASS_MAX_ITEMS; ++i) tab.it[i] = tab.it[0];
-  for (int a = 0; a < n_out; ++a) {
-    for (int b = 0; b < n_in; ++b) UZ_REQUIRE(!bl_overlap(outr[a], in[b]), "uz_boundary_loss: tensors overlap");
-    for (int b = a + 1; b < n_out; ++b) UZ_REQUIRE(!bl_overlap(outr[a], outr[b]), "uz_boundary_loss: tensors overlap");
-  }
+  bool any_grad;      // the loss launch serves both: unused here
+  const int irc = uz_map_items("uz_boundary_loss", items, d->n_items, map_bytes, in, &n_in, outr, &n_out, &any_grad, tab.it);
+  if (irc != UZ_OK) return irc;
+  UZ_REQUIRE(!uz_any_overlap(outr, n_out, in, n_in), "uz_boundary_loss: tensors overlap");
   char* base = static_cast<char*>(workspace);
   unsigned short* gw = reinterpret_cast<unsigned short*>(base + p.off[0]);
   int* cnt = reinterpret_cast<int*>(base + p.off[1]);
   double* part = reinterpret_cast<double*>(base + p.off[2]);
   int2* rowinfo = reinterpret_cast<int2*>(base + p.off[3]);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int cap = 8 * UZ_NUM_CU_HW;
   const dim3 block(BL_THREADS);
   const bool cls = d->mode == UZ_BOUNDARY_CLASS;
 
-  const long long rows = (long long)g.M * g.H;
-  const dim3 rgrid((unsigned)(rows < cap ? rows : cap));
+  const dim3 rgrid((unsigned)p.rows_grid);
   if (cls) hipLaunchKernelGGL((boundary_rows_kernel<UZ_BOUNDARY_CLASS>), rgrid, block, 0, s, g, target, gw, rowinfo);
   else hipLaunchKernelGGL((boundary_rows_kernel<UZ_BOUNDARY_BINARY>), rgrid, block, 0, s, g, target, gw, rowinfo);
   UZ_LAUNCH_CHECK("uz_boundary_loss(rows)");
-  hipLaunchKernelGGL(boundary_planes_kernel, dim3((unsigned)(g.M < cap ? g.M : cap)), block, 0, s, g, (const int2*)rowinfo, cnt);
+  hipLaunchKernelGGL(boundary_planes_kernel, dim3((unsigned)p.planes_grid), block, 0, s, g, (const int2*)rowinfo, cnt);
   UZ_LAUNCH_CHECK("uz_boundary_loss(planes)");
   hipLaunchKernelGGL(boundary_columns_kernel, dim3((unsigned)p.grid), block, 0, s, g, (const unsigned short*)gw, (const int*)cnt, sd2);
   UZ_LAUNCH_CHECK("uz_boundary_loss(columns)");

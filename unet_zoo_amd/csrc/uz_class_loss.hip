@@ -610,7 +610,7 @@ extern "C" long long uz_class_loss_workspace_bytes(const uz_class_desc* d) {
   ClPlan p;
   if (cl_plan("uz_class_loss_workspace_bytes", d, &p) != UZ_OK) return -1;
   const long long bytes = cl_doubles(p) * (long long)sizeof(double) + (long long)p.pairs * (2 * d->K + 2) * (long long)sizeof(float);
-  return (bytes + 15) / 16 * 16;
+  return uz_align16(bytes);
 }
 
 extern "C" int uz_class_loss(const uz_class_desc* d, const uz_class_item* items, const int* labels, const float* class_weight,

@@ -565,8 +565,6 @@ __global__ __launch_bounds__(CD_PT) void cldice_grad_class_kernel(const CdItems 
 }
 
 // --------------------------------------------------------------------------------------------------------------------- host
-long long cd_align(long long b) { return (b + 15) / 16 * 16; }
-
 enum { CD_PROB, CD_TPL, CD_DPROB, CD_PART, CD_COEF, CD_CL, CD_NBUF };
 
 struct CdPlan {
@@ -610,27 +608,14 @@ int cd_plan(const uz_cldice_desc* d, const char* who, CdPlan* p) {
   g.E = E;
   g.pixels = pixels;
   // four workgroups per CU of the hardware; more units than that are walked
-  const int cap = 4 * UZ_NUM_CU_HW;
-  p->grid = g.units < cap ? g.units : cap;
-  p->tgrid = g.tunits < cap ? g.tunits : cap;
-  const long long sb = ((cls ? pixels : E) + CD_PT - 1) / CD_PT;
-  p->stream_grid = (int)(sb < 8 * UZ_NUM_CU_HW ? sb : 8 * UZ_NUM_CU_HW);
+  p->grid = uz_grid_cap(g.units, 4);
+  p->tgrid = uz_grid_cap(g.tunits, 4);
+  p->stream_grid = uz_grid_cap(((cls ? pixels : E) + CD_PT - 1) / CD_PT, 8);
   const long long pairs = (long long)d->n_items * g.nseg;
   const long long sizes[CD_NBUF] = {4 * E * d->n_items, cls ? 4 * E : 0, 4 * E * d->n_items, 32LL * g.units, 24 * pairs, 8 * pairs};
-  long long at = 0;
-  for (int e = 0; e < CD_NBUF; ++e) {
-    p->off[e] = at;
-    at += cd_align(sizes[e]);
-  }
-  p->bytes = at;
+  p->bytes = uz_carve(sizes, CD_NBUF, p->off);
   return UZ_OK;
 }
-
-struct CdRange {
-  uintptr_t lo, hi;
-};
-CdRange cd_range(const void* p, long long bytes) { return {(uintptr_t)p, (uintptr_t)p + (uintptr_t)bytes}; }
-bool cd_overlap(const CdRange& x, const CdRange& y) { return x.lo < y.hi && y.lo < x.hi; }
 
 template <int KMAX>
 void cd_tiles(const CdPlan& p, const float* prob, const float* tpl, float* tskel, float* skeleton, double* part,
@@ -677,35 +662,15 @@ extern "C" int uz_cldice_loss(const uz_cldice_desc* d, const uz_cldice_item* ite
   const bool cls = d->mode == UZ_CLDICE_CLASS;
   const long long map_bytes = 4LL * g.E;
   // what the call writes (out, the three plane outputs, workspace, every dlogits) against everything else it touches
-  CdRange in[3 + UZ_CLASS_MAX_ITEMS], outr[5 + UZ_CLASS_MAX_ITEMS];
-  int n_in = 0, n_out = 0;
-  in[n_in++] = cd_range(target, cls ? 4LL * g.pixels : map_bytes);
-  in[n_in++] = cd_range(scales, 8);
-  in[n_in++] = cd_range(base_loss, 4);
-  outr[n_out++] = cd_range(out, 8);
-  outr[n_out++] = cd_range(probs, map_bytes);
-  outr[n_out++] = cd_range(skeleton, map_bytes);
-  outr[n_out++] = cd_range(target_skeleton, map_bytes);
-  outr[n_out++] = cd_range(workspace, p.bytes);
+  UzRange in[3 + UZ_CLASS_MAX_ITEMS] = {uz_range(target, cls ? 4LL * g.pixels : map_bytes), uz_range(scales, 8), uz_range(base_loss, 4)};
+  UzRange outr[5 + UZ_CLASS_MAX_ITEMS] = {uz_range(out, 8), uz_range(probs, map_bytes), uz_range(skeleton, map_bytes),
+                                          uz_range(target_skeleton, map_bytes), uz_range(workspace, p.bytes)};
+  int n_in = 3, n_out = 5;
   CdItems tab;
-  bool any_grad = false;
-  for (int i = 0; i < d->n_items; ++i) {
-    const uz_cldice_item& it = items[i];
-    UZ_REQUIRE(it.logits != nullptr, "uz_cldice_loss: item %d has null logits", i);
-    UZ_REQUIRE((((uintptr_t)it.logits | (uintptr_t)it.dlogits) & 3) == 0, "uz_cldice_loss: tensors must be 4-byte aligned");
-    UZ_REQUIRE(it.weight >= 0.f && it.weight < INFINITY, "uz_cldice_loss: item %d has a negative weight", i);
-    in[n_in++] = cd_range(it.logits, map_bytes);
-    if (it.dlogits != nullptr) {
-      outr[n_out++] = cd_range(it.dlogits, map_bytes);
-      any_grad = true;
-    }
-    tab.it[i] = it;
-  }
-  for (int i = d->n_items; i < UZ_CLASS_MAX_ITEMS; ++i) tab.it[i] = tab.it[0];
-  for (int a = 0; a < n_out; ++a) {
-    for (int b = 0; b < n_in; ++b) UZ_REQUIRE(!cd_overlap(outr[a], in[b]), "uz_cldice_loss: tensors overlap");
-    for (int b = a + 1; b < n_out; ++b) UZ_REQUIRE(!cd_overlap(outr[a], outr[b]), "uz_cldice_loss: tensors overlap");
-  }
+  bool any_grad;
+  const int irc = uz_map_items("uz_cldice_loss", items, d->n_items, map_bytes, in, &n_in, outr, &n_out, &any_grad, tab.it);
+  if (irc != UZ_OK) return irc;
+  UZ_REQUIRE(!uz_any_overlap(outr, n_out, in, n_in), "uz_cldice_loss: tensors overlap");
   char* base = static_cast<char*>(workspace);
   float* prob = reinterpret_cast<float*>(base + p.off[CD_PROB]);
   float* tplw = reinterpret_cast<float*>(base + p.off[CD_TPL]);

@@ -57,6 +57,8 @@ void uz_set_error(const char* fmt, ...);
     }                                                                       \
   } while (0)
 
+#include "uz_host.h"   // ranges, workspace carve, grid cap, item table: the host scaffold of the descriptor passes
+
 template <typename T> struct ElemTraits;
 template <> struct ElemTraits<float> {
   static constexpr int VEC = 4;  // elements per 16 bytes

@@ -260,11 +260,10 @@ __global__ __launch_bounds__(CF_THREADS) void confusion_finalize_class_kernel(Cf
   }
 }
 
-long long cf_align(long long b) { return (b + 15) / 16 * 16; }
-
 struct CfPlan {
   CfGeo geo;
   int grid;                  // the counting pass
+  int clear_grid;
   long long off_hist;        // binary: bytes from the counts to the histograms
   long long bytes;
 };
@@ -297,24 +296,19 @@ int cf_plan(const uz_confusion_desc* d, const char* who, CfPlan* p) {
   g.B = cls ? 0 : d->bins;
   g.ignore_index = d->ignore_index;
   // eight workgroups of four waves per CU of the hardware: what can be resident at once; more units than that are walked
-  int grid = g.units < 8 * UZ_NUM_CU_HW ? g.units : 8 * UZ_NUM_CU_HW;
+  int grid = uz_grid_cap(g.units, 8);
   if (d->max_workgroups > 0 && grid > d->max_workgroups) grid = d->max_workgroups;
   p->grid = grid;
   if (cls) {
     p->off_hist = 0;
-    p->bytes = cf_align(4LL * g.M * g.K * g.K);
+    p->bytes = uz_align16(4LL * g.M * g.K * g.K);
   } else {
-    p->off_hist = cf_align(16LL * g.M);
-    p->bytes = p->off_hist + cf_align(8LL * g.M * g.B);
+    p->off_hist = uz_align16(16LL * g.M);
+    p->bytes = p->off_hist + uz_align16(8LL * g.M * g.B);
   }
+  p->clear_grid = uz_grid_cap(uz_cdiv(p->bytes / 16, CF_THREADS), 8);
   return UZ_OK;
 }
-
-struct CfRange {
-  uintptr_t lo, hi;
-};
-CfRange cf_range(const void* p, long long bytes) { return {(uintptr_t)p, (uintptr_t)p + (uintptr_t)bytes}; }
-bool cf_overlap(const CfRange& x, const CfRange& y) { return x.lo < y.hi && y.lo < x.hi; }
 
 }  // namespace
 
@@ -349,23 +343,18 @@ extern "C" int uz_confusion_metrics(const uz_confusion_desc* d, const float* log
   UZ_REQUIRE(((uintptr_t)counts & 7) == 0 && (cls || ((uintptr_t)hist & 7) == 0), "uz_confusion_metrics: counts and hist must be 8-byte aligned");
   UZ_REQUIRE(((uintptr_t)workspace & 15) == 0, "uz_confusion_metrics: the workspace must be 16-byte aligned");
   const long long px = (long long)d->N * d->H * d->W;
-  CfRange r[7] = {cf_range(logits, 4LL * px * d->C), cf_range(target, cls ? 4LL * px : 4LL * px * d->C),
-                  cf_range(counts, cls ? 8LL * g.M * g.K * g.K : 32LL * g.M), cf_range(out, 32LL * d->N * g.P), cf_range(workspace, p.bytes),
-                  cf_range(edges, 4LL * (g.B - 1)), cf_range(hist, 16LL * g.M * g.B)};
-  const int nr = cls ? 5 : 7;
-  for (int a = 0; a < nr; ++a)
-    for (int b = a + 1; b < nr; ++b) UZ_REQUIRE(!cf_overlap(r[a], r[b]), "uz_confusion_metrics: tensors overlap");
+  const UzRange r[7] = {uz_range(logits, 4LL * px * d->C), uz_range(target, cls ? 4LL * px : 4LL * px * d->C),
+                        uz_range(counts, cls ? 8LL * g.M * g.K * g.K : 32LL * g.M), uz_range(out, 32LL * d->N * g.P),
+                        uz_range(workspace, p.bytes), uz_range(edges, 4LL * (g.B - 1)), uz_range(hist, 16LL * g.M * g.B)};
+  UZ_REQUIRE(!uz_any_overlap(r, 7, nullptr, 0), "uz_confusion_metrics: tensors overlap");      // class mode: B = 0, edges and hist are empty
   int* wcnt = static_cast<int*>(workspace);
   int* whist = reinterpret_cast<int*>(static_cast<char*>(workspace) + p.off_hist);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int cap = 8 * UZ_NUM_CU_HW;
   const dim3 block(CF_THREADS);
   // the 16-byte path: every plane starts on a 16-byte boundary and holds whole quads
   const bool vec = g.HW % 4 == 0 && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)target & 15) == 0;
 
-  const long long n4 = p.bytes / 16;
-  hipLaunchKernelGGL(confusion_clear_kernel, dim3((unsigned)(uz_cdiv(n4, CF_THREADS) < cap ? uz_cdiv(n4, CF_THREADS) : cap)), block, 0, s,
-                     reinterpret_cast<int4*>(workspace), n4);
+  hipLaunchKernelGGL(confusion_clear_kernel, dim3((unsigned)p.clear_grid), block, 0, s, reinterpret_cast<int4*>(workspace), p.bytes / 16);
   UZ_LAUNCH_CHECK("uz_confusion_metrics(clear)");
   if (cls) {
     const int* y = static_cast<const int*>(target);

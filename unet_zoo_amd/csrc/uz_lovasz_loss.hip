@@ -465,8 +465,6 @@ __global__ __launch_bounds__(LV_THREADS) void lovasz_finalize_kernel(const LvIte
   }
 }
 
-long long lv_align(long long b) { return (b + 15) / 16 * 16; }
-
 enum { LV_KEY_A, LV_VAL_A, LV_KEY_B, LV_VAL_B, LV_HIST, LV_DTOT, LV_TILE_G, LV_TILE_B, LV_SEG_G, LV_WSEG, LV_PART, LV_NBUF };
 
 struct LvPlan {
@@ -509,33 +507,17 @@ int lv_plan(const uz_lovasz_desc* d, const char* who, LvPlan* p) {
   g.E = E;
   g.pixels = pixels;
   // eight workgroups of four waves per CU of the hardware: what can be resident at once; more units than that are walked
-  const int cap = 8 * UZ_NUM_CU_HW;
-  p->grid = g.units < cap ? g.units : cap;
-  const int ku = cls ? g.punits : g.units;
-  p->keys_grid = ku < cap ? ku : cap;
-  const int su = d->n_items * g.lines;
-  p->seg_grid = su < cap ? su : cap;
-  const int ru = uz_cdiv((long long)g.GS * LV_BINS, LV_WAVES);
-  p->row_grid = ru < cap ? ru : cap;
-  const long long gb = ((cls ? pixels : E) + LV_THREADS - 1) / LV_THREADS;
-  p->grad_grid = (int)(gb < cap ? gb : cap);
+  p->grid = uz_grid_cap(g.units, 8);
+  p->keys_grid = uz_grid_cap(cls ? g.punits : g.units, 8);
+  p->seg_grid = uz_grid_cap(d->n_items * g.lines, 8);
+  p->row_grid = uz_grid_cap(uz_cdiv((long long)g.GS * LV_BINS, LV_WAVES), 8);
+  p->grad_grid = uz_grid_cap(((cls ? pixels : E) + LV_THREADS - 1) / LV_THREADS, 8);
   const long long TE = E * d->n_items;
   const long long sizes[LV_NBUF] = {4 * TE, 4 * TE, 4 * TE, 4 * TE, 4LL * g.GS * LV_BINS * g.tps, 4LL * g.GS * LV_BINS,
                                     4LL * g.units, 4LL * g.units, 4LL * g.GS, 8LL * g.GS, 8LL * g.units};
-  long long at = 0;
-  for (int e = 0; e < LV_NBUF; ++e) {
-    p->off[e] = at;
-    at += lv_align(sizes[e]);
-  }
-  p->bytes = at;
+  p->bytes = uz_carve(sizes, LV_NBUF, p->off);
   return UZ_OK;
 }
-
-struct LvRange {
-  uintptr_t lo, hi;
-};
-LvRange lv_range(const void* p, long long bytes) { return {(uintptr_t)p, (uintptr_t)p + (uintptr_t)bytes}; }
-bool lv_overlap(const LvRange& x, const LvRange& y) { return x.lo < y.hi && y.lo < x.hi; }
 
 }  // namespace
 
@@ -566,34 +548,15 @@ extern "C" int uz_lovasz_loss(const uz_lovasz_desc* d, const uz_lovasz_item* ite
   const bool cls = d->mode == UZ_LOVASZ_CLASS;
   const long long map_bytes = 4LL * g.E;
   // what the call writes (out, errors, ranks, workspace, every dlogits) against everything else it touches
-  LvRange in[3 + UZ_CLASS_MAX_ITEMS], outr[4 + UZ_CLASS_MAX_ITEMS];
-  int n_in = 0, n_out = 0;
-  in[n_in++] = lv_range(target, cls ? 4LL * g.pixels : map_bytes);
-  in[n_in++] = lv_range(scales, 8);
-  in[n_in++] = lv_range(base_loss, 4);
-  outr[n_out++] = lv_range(out, 8);
-  outr[n_out++] = lv_range(errors, map_bytes);
-  outr[n_out++] = lv_range(ranks, map_bytes);
-  outr[n_out++] = lv_range(workspace, p.bytes);
+  UzRange in[3 + UZ_CLASS_MAX_ITEMS] = {uz_range(target, cls ? 4LL * g.pixels : map_bytes), uz_range(scales, 8), uz_range(base_loss, 4)};
+  UzRange outr[4 + UZ_CLASS_MAX_ITEMS] = {uz_range(out, 8), uz_range(errors, map_bytes), uz_range(ranks, map_bytes),
+                                          uz_range(workspace, p.bytes)};
+  int n_in = 3, n_out = 4;
   LvItems tab;
-  bool any_grad = false;
-  for (int i = 0; i < d->n_items; ++i) {
-    const uz_lovasz_item& it = items[i];
-    UZ_REQUIRE(it.logits != nullptr, "uz_lovasz_loss: item %d has null logits", i);
-    UZ_REQUIRE((((uintptr_t)it.logits | (uintptr_t)it.dlogits) & 3) == 0, "uz_lovasz_loss: tensors must be 4-byte aligned");
-    UZ_REQUIRE(it.weight >= 0.f && it.weight < INFINITY, "uz_lovasz_loss: item %d has a negative weight", i);
-    in[n_in++] = lv_range(it.logits, map_bytes);
-    if (it.dlogits != nullptr) {
-      outr[n_out++] = lv_range(it.dlogits, map_bytes);
-      any_grad = true;
-    }
-    tab.it[i] = it;
-  }
-  for (int i = d->n_items; i < UZ_CLASS_MAX_ITEMS; ++i) tab.it[i] = tab.it[0];
-  for (int a = 0; a < n_out; ++a) {
-    for (int b = 0; b < n_in; ++b) UZ_REQUIRE(!lv_overlap(outr[a], in[b]), "uz_lovasz_loss: tensors overlap");
-    for (int b = a + 1; b < n_out; ++b) UZ_REQUIRE(!lv_overlap(outr[a], outr[b]), "uz_lovasz_loss: tensors overlap");
-  }
+  bool any_grad;
+  const int irc = uz_map_items("uz_lovasz_loss", items, d->n_items, map_bytes, in, &n_in, outr, &n_out, &any_grad, tab.it);
+  if (irc != UZ_OK) return irc;
+  UZ_REQUIRE(!uz_any_overlap(outr, n_out, in, n_in), "uz_lovasz_loss: tensors overlap");
   char* base = static_cast<char*>(workspace);
   unsigned* kv[2][2] = {{reinterpret_cast<unsigned*>(base + p.off[LV_KEY_A]), reinterpret_cast<unsigned*>(base + p.off[LV_VAL_A])},
                         {reinterpret_cast<unsigned*>(base + p.off[LV_KEY_B]), reinterpret_cast<unsigned*>(base + p.off[LV_VAL_B])}};

@@ -297,12 +297,6 @@ int patch_check(const uz_patch_desc* d, const char* who) {
   return UZ_OK;
 }
 
-struct PatchRange {
-  uintptr_t lo, hi;
-};
-PatchRange patch_range(const void* p, long long bytes) { return {(uintptr_t)p, (uintptr_t)p + (uintptr_t)bytes}; }
-bool patch_overlap(const PatchRange& x, const PatchRange& y) { return x.lo < y.hi && y.lo < x.hi; }
-
 long long patch_index_bytes(const uz_patch_desc* d) { return 4LL * d->M * d->P * ((long long)d->H + 1); }
 long long patch_mask_bytes(const uz_patch_desc* d) {
   const long long px = (long long)d->M * d->H * d->W;
@@ -325,8 +319,7 @@ int patch_plan(const uz_patch_desc* d, const char* who, PatchPlan* p) {
   s.Cm = d->mask_kind == UZ_PATCH_MASK_F32 ? d->Cm : 1;
   s.vec = 0;
   // eight workgroups of four waves per CU of the hardware: what can be resident at once; more units than that are walked
-  const int cap = 8 * UZ_NUM_CU_HW;
-  p->grid = s.units < cap ? s.units : cap;
+  p->grid = uz_grid_cap(s.units, 8);
   return UZ_OK;
 }
 
@@ -365,7 +358,7 @@ extern "C" int uz_patch_index(const uz_patch_desc* d, const void* mask, int* ind
   UZ_REQUIRE(d->mask_kind != UZ_PATCH_MASK_NONE, "uz_patch_index: mask_kind none has no foreground planes to index");
   UZ_REQUIRE(mask && index, "uz_patch_index: null pointer");
   UZ_REQUIRE(((uintptr_t)mask & 3) == 0 && ((uintptr_t)index & 3) == 0, "uz_patch_index: tensors must be 4-byte aligned");
-  UZ_REQUIRE(!patch_overlap(patch_range(mask, patch_mask_bytes(d)), patch_range(index, patch_index_bytes(d))),
+  UZ_REQUIRE(!uz_overlap(uz_range(mask, patch_mask_bytes(d)), uz_range(index, patch_index_bytes(d))),
              "uz_patch_index: mask and index overlap");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const long long rows = (long long)d->M * d->P * d->H;   // < 2^31 (patch_check)
@@ -390,10 +383,10 @@ extern "C" int uz_patch_draw(const uz_patch_desc* d, const float* u, const int* 
   UZ_REQUIRE(((uintptr_t)u & 3) == 0 && ((uintptr_t)indices & 3) == 0 && ((uintptr_t)index & 3) == 0 && ((uintptr_t)mask & 3) == 0 &&
                  ((uintptr_t)coords & 3) == 0,
              "uz_patch_draw: tensors must be 4-byte aligned");
-  const PatchRange out = patch_range(coords, 16LL * d->B);
-  const PatchRange in[4] = {patch_range(u, 32LL * d->B), patch_range(indices, indices ? 4LL * d->B : 0),
-                            patch_range(index, index ? patch_index_bytes(d) : 0), patch_range(mask, patch_mask_bytes(d))};
-  for (int i = 0; i < 4; ++i) UZ_REQUIRE(!patch_overlap(out, in[i]), "uz_patch_draw: coords overlap an input");
+  const UzRange out = uz_range(coords, 16LL * d->B);
+  const UzRange in[4] = {uz_range(u, 32LL * d->B), uz_range(indices, 4LL * d->B), uz_range(index, patch_index_bytes(d)),
+                         uz_range(mask, patch_mask_bytes(d))};
+  UZ_REQUIRE(!uz_any_overlap(&out, 1, in, 4), "uz_patch_draw: coords overlap an input");
   PatchDraw a;
   a.M = d->M, a.H = d->H, a.W = d->W, a.mask_kind = d->mask_kind, a.Cm = d->Cm, a.P = d->P, a.h = d->h, a.w = d->w;
   a.use_indices = d->use_indices, a.pos = d->pos, a.jitter = d->jitter;
@@ -426,12 +419,11 @@ extern "C" int uz_patch_cut(const uz_patch_desc* d, const void* image, const voi
              "uz_patch_cut: tensors must be 4-byte aligned");
   const long long opx = (long long)d->B * d->h * d->w;
   const long long ombytes = d->mask_kind == UZ_PATCH_MASK_NONE ? 0 : 4LL * opx * p.sh.Cm;
-  const PatchRange in[4] = {patch_range(image, (long long)esz * d->M * d->C * d->H * d->W), patch_range(mask, patch_mask_bytes(d)),
-                            patch_range(coords, 16LL * d->B), patch_range(norm, norm ? 8LL * d->C : 0)};
-  const PatchRange out[2] = {patch_range(image_out, 4LL * opx * d->C), patch_range(mask_out, ombytes)};
-  for (int o = 0; o < 2; ++o)
-    for (int i = 0; i < 4; ++i) UZ_REQUIRE(!patch_overlap(out[o], in[i]), "uz_patch_cut: an output overlaps an input");
-  UZ_REQUIRE(!patch_overlap(out[0], out[1]), "uz_patch_cut: the two outputs overlap");
+  const UzRange in[4] = {uz_range(image, (long long)esz * d->M * d->C * d->H * d->W), uz_range(mask, patch_mask_bytes(d)),
+                         uz_range(coords, 16LL * d->B), uz_range(norm, 8LL * d->C)};
+  const UzRange out[2] = {uz_range(image_out, 4LL * opx * d->C), uz_range(mask_out, ombytes)};
+  UZ_REQUIRE(!uz_any_overlap(&out[0], 1, in, 4) && !uz_any_overlap(&out[1], 1, in, 4), "uz_patch_cut: an output overlaps an input");
+  UZ_REQUIRE(!uz_any_overlap(out, 2, nullptr, 0), "uz_patch_cut: the two outputs overlap");
   p.sh.vec = d->w % 4 == 0 && ((uintptr_t)image_out & 15) == 0 && ((uintptr_t)mask_out & 15) == 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (d->image_kind == UZ_PATCH_IMAGE_U8) patch_launch_c<unsigned char>(d->C, d->mask_kind, p, s, image, mask, coords, norm, image_out, mask_out);

@@ -382,11 +382,10 @@ __global__ __launch_bounds__(PP_THREADS) void postproc_classmap_kernel(PpGeo geo
   }
 }
 
-long long pp_align(long long b) { return (b + 15) / 16 * 16; }
-
 struct PpPlan {
   PpGeo geo;
   int grid;                     // the per-unit launches
+  int clear_grid, codes_grid, scan_grid, fin_grid;
   long long off[9], bytes;      // codes, set, parent, area, ucnt, uoff, cnt, top, acc
 };
 
@@ -420,25 +419,17 @@ int pp_plan(const uz_postproc_desc* d, const char* who, PpPlan* p) {
   g.conn = d->connectivity, g.min_area = d->min_area, g.keep = d->keep_largest;
   g.thr = d->thr;
   // eight workgroups of four waves per CU of the hardware: what can be resident at once; more units than that are walked
-  const int cap = 8 * UZ_NUM_CU_HW;
-  p->grid = g.units < cap ? g.units : cap;
+  p->grid = uz_grid_cap(g.units, 8);
+  p->codes_grid = uz_grid_cap(((long long)g.M * g.HW + PP_THREADS - 1) / PP_THREADS, 8);
+  p->scan_grid = uz_grid_cap(g.NP, 8);
+  p->fin_grid = uz_cdiv(g.NP, PP_THREADS);
   const long long px = (long long)g.NP * g.HW;
   const long long sizes[9] = {(long long)g.M * g.HW, px, 4 * px, 4 * px, 4LL * g.units, 4LL * g.units, 8LL * g.NP * PP_CNT, 8LL * g.NP * 8,
                               8LL * g.NP * 8 * PP_ACC};
-  long long at = 0;
-  for (int e = 0; e < 9; ++e) {
-    p->off[e] = at;
-    at += pp_align(sizes[e]);
-  }
-  p->bytes = at;
+  p->bytes = uz_carve(sizes, 9, p->off);
+  p->clear_grid = uz_grid_cap(uz_cdiv((p->bytes - p->off[6]) / 16, PP_THREADS), 8);      // cnt, top, acc as int4
   return UZ_OK;
 }
-
-struct PpRange {
-  uintptr_t lo, hi;
-};
-PpRange pp_range(const void* p, long long bytes) { return {(uintptr_t)p, (uintptr_t)p + (uintptr_t)(p ? bytes : 0)}; }
-bool pp_overlap(const PpRange& x, const PpRange& y) { return x.lo < y.hi && y.lo < x.hi; }
 
 }  // namespace
 
@@ -468,11 +459,10 @@ extern "C" int uz_postproc(const uz_postproc_desc* d, const float* x, unsigned c
   UZ_REQUIRE(((uintptr_t)workspace & 15) == 0, "uz_postproc: the workspace must be 16-byte aligned");
   const PpGeo& g = p.geo;
   const long long px = (long long)g.NP * g.HW;
-  const PpRange r[7] = {pp_range(x, 4LL * d->N * d->C * g.HW), pp_range(mask, px), pp_range(labels, 4 * px),
-                        pp_range(class_map, (long long)g.M * g.HW), pp_range(stats, 64LL * g.NP), pp_range(comps, 512LL * g.NP),
-                        pp_range(workspace, p.bytes)};
-  for (int a = 0; a < 7; ++a)
-    for (int b = a + 1; b < 7; ++b) UZ_REQUIRE(!pp_overlap(r[a], r[b]), "uz_postproc: tensors overlap");
+  const UzRange r[7] = {uz_range(x, 4LL * d->N * d->C * g.HW), uz_range(mask, px), uz_range(labels, 4 * px),
+                        uz_range(class_map, (long long)g.M * g.HW), uz_range(stats, 64LL * g.NP), uz_range(comps, 512LL * g.NP),
+                        uz_range(workspace, p.bytes)};
+  UZ_REQUIRE(!uz_any_overlap(r, 7, nullptr, 0), "uz_postproc: tensors overlap");
   char* base = static_cast<char*>(workspace);
   PpWs ws;
   ws.codes = reinterpret_cast<unsigned char*>(base + p.off[0]);
@@ -485,15 +475,11 @@ extern "C" int uz_postproc(const uz_postproc_desc* d, const float* x, unsigned c
   ws.top = reinterpret_cast<unsigned long long*>(base + p.off[7]);
   ws.acc = reinterpret_cast<long long*>(base + p.off[8]);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int cap = 8 * UZ_NUM_CU_HW;
-  const dim3 block(PP_THREADS), ugrid((unsigned)p.grid);
+  const dim3 block(PP_THREADS), ugrid((unsigned)p.grid), cgrid((unsigned)p.codes_grid);
 
-  const long long n4 = (p.bytes - p.off[6]) / 16;
-  hipLaunchKernelGGL(postproc_clear_kernel, dim3((unsigned)(uz_cdiv(n4, PP_THREADS) < cap ? uz_cdiv(n4, PP_THREADS) : cap)), block, 0, s,
-                     reinterpret_cast<int4*>(ws.cnt), n4);
+  hipLaunchKernelGGL(postproc_clear_kernel, dim3((unsigned)p.clear_grid), block, 0, s, reinterpret_cast<int4*>(ws.cnt),
+                     (p.bytes - p.off[6]) / 16);
   UZ_LAUNCH_CHECK("uz_postproc(clear)");
-  const long long cblocks = ((long long)g.M * g.HW + PP_THREADS - 1) / PP_THREADS;
-  const dim3 cgrid((unsigned)(cblocks < cap ? cblocks : cap));
   if (d->mode == UZ_POST_BINARY) hipLaunchKernelGGL((postproc_codes_kernel<UZ_POST_BINARY>), cgrid, block, 0, s, g, x, ws.codes);
   else hipLaunchKernelGGL((postproc_codes_kernel<UZ_POST_CLASS>), cgrid, block, 0, s, g, x, ws.codes);
   UZ_LAUNCH_CHECK("uz_postproc(codes)");
@@ -523,7 +509,7 @@ extern "C" int uz_postproc(const uz_postproc_desc* d, const float* x, unsigned c
   hipLaunchKernelGGL(postproc_keep_kernel, ugrid, block, 0, s, g, (const unsigned char*)ws.set, (const int*)ws.parent, (const int*)ws.area,
                      (const unsigned long long*)ws.top, mask, ws.ucnt, ws.cnt, ws.acc);
   UZ_LAUNCH_CHECK("uz_postproc(keep)");
-  hipLaunchKernelGGL(postproc_scan_kernel, dim3((unsigned)(g.NP < cap ? g.NP : cap)), block, 0, s, g, (const int*)ws.ucnt, ws.uoff, ws.cnt);
+  hipLaunchKernelGGL(postproc_scan_kernel, dim3((unsigned)p.scan_grid), block, 0, s, g, (const int*)ws.ucnt, ws.uoff, ws.cnt);
   UZ_LAUNCH_CHECK("uz_postproc(scan)");
   // launched whether or not the optional outputs are asked for: the launches of a call depend on the descriptor alone
   hipLaunchKernelGGL(postproc_number_kernel, ugrid, block, 0, s, g, (const unsigned char*)mask, (const int*)ws.parent, (const int*)ws.uoff,
@@ -532,7 +518,7 @@ extern "C" int uz_postproc(const uz_postproc_desc* d, const float* x, unsigned c
   hipLaunchKernelGGL(postproc_apply_kernel, ugrid, block, 0, s, g, (const unsigned char*)mask, (const int*)ws.parent, (const int*)ws.area,
                      labels);
   UZ_LAUNCH_CHECK("uz_postproc(apply)");
-  hipLaunchKernelGGL(postproc_finalize_kernel, dim3((unsigned)uz_cdiv(g.NP, PP_THREADS)), block, 0, s, g, (const long long*)ws.cnt,
+  hipLaunchKernelGGL(postproc_finalize_kernel, dim3((unsigned)p.fin_grid), block, 0, s, g, (const long long*)ws.cnt,
                      (const unsigned long long*)ws.top, (const long long*)ws.acc, stats, comps);
   UZ_LAUNCH_CHECK("uz_postproc(finalize)");
   if (d->mode == UZ_POST_CLASS) {

@@ -400,11 +400,10 @@ __global__ __launch_bounds__(SF_THREADS) void surface_finalize_kernel(SfGeo geo,
   }
 }
 
-long long sf_align(long long b) { return (b + 15) / 16 * 16; }
-
 struct SfPlan {
   SfGeo geo;
   int grid;                     // the column pass and the second histogram
+  int clear_grid, codes_grid, rows_grid;
   long long off[9], bytes;      // codes, g, d2, part, nq, cnt, hist1, hist2, sel
 };
 
@@ -435,25 +434,16 @@ int sf_plan(const uz_surface_desc* d, const char* who, SfPlan* p) {
   g.units = 2 * g.NP * g.tiles;
   g.ignore_index = d->ignore_index;
   // eight workgroups of four waves per CU of the hardware: what can be resident at once; more units than that are walked
-  const int cap = 8 * UZ_NUM_CU_HW;
-  p->grid = g.units < cap ? g.units : cap;
+  p->grid = uz_grid_cap(g.units, 8);
+  p->codes_grid = uz_grid_cap(((long long)g.M * g.HW + SF_THREADS - 1) / SF_THREADS, 8);
+  p->rows_grid = uz_grid_cap((long long)g.M * g.H, 8);
   const long long planes = 2LL * g.NP * g.HW;
   const long long sizes[9] = {2LL * g.M * g.HW, 2 * planes, 4 * planes, 8LL * g.units, 4LL * g.units, 4LL * g.NP * SF_CNT,
                               4LL * g.NP * SF_BINS1, 8LL * g.NP * SF_BINS2, 16LL * g.NP};
-  long long at = 0;
-  for (int e = 0; e < 9; ++e) {
-    p->off[e] = at;
-    at += sf_align(sizes[e]);
-  }
-  p->bytes = at;
+  p->bytes = uz_carve(sizes, 9, p->off);
+  p->clear_grid = uz_grid_cap(uz_cdiv((p->off[8] - p->off[5]) / 16, SF_THREADS), 8);      // cnt, hist1, hist2 as int4
   return UZ_OK;
 }
-
-struct SfRange {
-  uintptr_t lo, hi;
-};
-SfRange sf_range(const void* p, long long bytes) { return {(uintptr_t)p, (uintptr_t)p + (uintptr_t)bytes}; }
-bool sf_overlap(const SfRange& x, const SfRange& y) { return x.lo < y.hi && y.lo < x.hi; }
 
 }  // namespace
 
@@ -483,10 +473,9 @@ extern "C" int uz_surface_metrics(const uz_surface_desc* d, const float* logits,
   UZ_REQUIRE(((uintptr_t)workspace & 15) == 0, "uz_surface_metrics: the workspace must be 16-byte aligned");
   const SfGeo& g = p.geo;
   const long long px = (long long)d->N * d->H * d->W;
-  const SfRange r[5] = {sf_range(logits, 4LL * px * d->C), sf_range(target, d->mode == UZ_SURFACE_CLASS ? 4LL * px : 4LL * px * d->C),
-                        sf_range(out, 16LL * g.NP), sf_range(stats, 64LL * g.NP), sf_range(workspace, p.bytes)};
-  for (int a = 0; a < 5; ++a)
-    for (int b = a + 1; b < 5; ++b) UZ_REQUIRE(!sf_overlap(r[a], r[b]), "uz_surface_metrics: tensors overlap");
+  const UzRange r[5] = {uz_range(logits, 4LL * px * d->C), uz_range(target, d->mode == UZ_SURFACE_CLASS ? 4LL * px : 4LL * px * d->C),
+                        uz_range(out, 16LL * g.NP), uz_range(stats, 64LL * g.NP), uz_range(workspace, p.bytes)};
+  UZ_REQUIRE(!uz_any_overlap(r, 5, nullptr, 0), "uz_surface_metrics: tensors overlap");
   char* base = static_cast<char*>(workspace);
   SfWs ws;
   ws.codes = reinterpret_cast<unsigned short*>(base + p.off[0]);
@@ -500,21 +489,16 @@ extern "C" int uz_surface_metrics(const uz_surface_desc* d, const float* logits,
   ws.sel = reinterpret_cast<int*>(base + p.off[8]);
   ws.nclear = (p.off[8] - p.off[5]) / 4;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int cap = 8 * UZ_NUM_CU_HW;
   const dim3 block(SF_THREADS);
   const double qf = d->q / 100.0;
 
-  const long long n4 = ws.nclear / 4;
-  hipLaunchKernelGGL(surface_clear_kernel, dim3((unsigned)(uz_cdiv(n4, SF_THREADS) < cap ? uz_cdiv(n4, SF_THREADS) : cap)), block, 0, s,
-                     reinterpret_cast<int4*>(ws.cnt), n4);
+  hipLaunchKernelGGL(surface_clear_kernel, dim3((unsigned)p.clear_grid), block, 0, s, reinterpret_cast<int4*>(ws.cnt), ws.nclear / 4);
   UZ_LAUNCH_CHECK("uz_surface_metrics(clear)");
-  const long long cblocks = ((long long)g.M * g.HW + SF_THREADS - 1) / SF_THREADS;
-  const dim3 cgrid((unsigned)(cblocks < cap ? cblocks : cap));
+  const dim3 cgrid((unsigned)p.codes_grid);
   if (d->mode == UZ_SURFACE_BINARY) hipLaunchKernelGGL((surface_codes_kernel<UZ_SURFACE_BINARY>), cgrid, block, 0, s, g, logits, target, ws.codes);
   else hipLaunchKernelGGL((surface_codes_kernel<UZ_SURFACE_CLASS>), cgrid, block, 0, s, g, logits, target, ws.codes);
   UZ_LAUNCH_CHECK("uz_surface_metrics(codes)");
-  const long long rows = (long long)g.M * g.H;
-  hipLaunchKernelGGL(surface_rows_kernel, dim3((unsigned)(rows < cap ? rows : cap)), block, 0, s, g, (const unsigned short*)ws.codes, ws.g, ws.cnt);
+  hipLaunchKernelGGL(surface_rows_kernel, dim3((unsigned)p.rows_grid), block, 0, s, g, (const unsigned short*)ws.codes, ws.g, ws.cnt);
   UZ_LAUNCH_CHECK("uz_surface_metrics(rows)");
   hipLaunchKernelGGL(surface_columns_kernel, dim3((unsigned)p.grid), block, 0, s, g, (const unsigned short*)ws.g, ws.d2, ws.part, ws.nq, ws.cnt, ws.hist1);
   UZ_LAUNCH_CHECK("uz_surface_metrics(columns)");

@@ -110,10 +110,7 @@ TlBlendFn tl_blend(int ky, int kx) {
   return ky <= 1 ? tl_blend_x<1>(kx) : ky <= 2 ? tl_blend_x<2>(kx) : ky <= 4 ? tl_blend_x<4>(kx) : tl_blend_x<8>(kx);
 }
 
-unsigned tl_grid(long long total) {
-  const long long b = (total + TL_THREADS - 1) / TL_THREADS, cap = 8LL * UZ_NUM_CU_HW;
-  return (unsigned)(b < cap ? b : cap);
-}
+unsigned tl_grid(long long total) { return (unsigned)uz_grid_cap((total + TL_THREADS - 1) / TL_THREADS, 8); }
 
 // the start table of one axis: strictly ascending from 0 to D - window, no gap; *cover = the most tiles over one pixel
 int tl_axis(const char* who, const char* axis, const int* starts, int n, int size, int window, int* cover) {
@@ -139,11 +136,6 @@ int tl_shape(const char* who, int N, int C, int H, int W, int th, int tw) {
   UZ_REQUIRE(th >= 1 && tw >= 1, "%s: non-positive window", who);
   UZ_REQUIRE((long long)N * C * H * W < (1LL << 31), "%s: too large (N C H W >= 2^31)", who);
   return UZ_OK;
-}
-
-bool tl_overlap(const void* a, long long na, const void* b, long long nb) {
-  const uintptr_t al = (uintptr_t)a, ah = al + 4 * na, bl = (uintptr_t)b, bh = bl + 4 * nb;
-  return al < bh && bl < ah;
 }
 
 void tl_tabs(TlTabs* t, const int* ys, int ny, const int* xs, int nx) {
@@ -184,7 +176,7 @@ extern "C" int uz_tile_gather(const uz_tile_gather_desc* d, const int* ys, const
   if (d->pad_mode == UZ_TILE_PAD_REFLECT)
     UZ_REQUIRE(py - oy < d->H && px - ox < d->W, "%s: reflect needs pad < size, got pads (%d, %d) on a %d x %d image", who, py - oy, px - ox, d->H, d->W);
   UZ_REQUIRE(((uintptr_t)x & 3) == 0 && ((uintptr_t)out & 3) == 0, "%s: a tensor is not 4-byte aligned", who);
-  UZ_REQUIRE(!tl_overlap(x, nx_, out, total), "%s: the output overlaps the input", who);
+  UZ_REQUIRE(!uz_overlap(uz_range(x, 4 * nx_), uz_range(out, 4 * total)), "%s: the output overlaps the input", who);
   TlTabs tab;
   tl_tabs(&tab, ys, d->ny, xs, d->nx);
   hipLaunchKernelGGL(tile_gather_kernel, dim3(tl_grid(total)), dim3(TL_THREADS), 0, static_cast<hipStream_t>(stream), tab, x, out, total, d->C, d->H,
@@ -206,8 +198,8 @@ extern "C" int uz_tile_blend(const uz_tile_blend_desc* d, const int* ys, const i
   const long long total = (long long)d->N * d->C * d->H * d->W, nt = (long long)d->N * d->ny * d->nx * d->C * d->th * d->tw;
   UZ_REQUIRE(nt < (1LL << 31), "%s: too large (T C th tw >= 2^31)", who);
   UZ_REQUIRE((((uintptr_t)tiles | (uintptr_t)gh | (uintptr_t)gw | (uintptr_t)out) & 3) == 0, "%s: a tensor is not 4-byte aligned", who);
-  UZ_REQUIRE(!tl_overlap(out, total, tiles, nt) && !tl_overlap(out, total, gh, d->th) && !tl_overlap(out, total, gw, d->tw),
-             "%s: the output overlaps an input", who);
+  const UzRange outr = uz_range(out, 4 * total), in[3] = {uz_range(tiles, 4 * nt), uz_range(gh, 4LL * d->th), uz_range(gw, 4LL * d->tw)};
+  UZ_REQUIRE(!uz_any_overlap(&outr, 1, in, 3), "%s: the output overlaps an input", who);
   const int oy = d->th > d->H ? (d->th - d->H) / 2 : 0, ox = d->tw > d->W ? (d->tw - d->W) / 2 : 0;
   TlTabs tab;
   tl_tabs(&tab, ys, d->ny, xs, d->nx);

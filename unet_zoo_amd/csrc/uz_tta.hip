@@ -131,10 +131,7 @@ int tt_check(const uz_tta_desc* d, const char* who) {
   return UZ_OK;
 }
 
-unsigned tt_grid(long long total) {
-  const long long b = (total + TT_THREADS - 1) / TT_THREADS, cap = 8LL * UZ_NUM_CU_HW;
-  return (unsigned)(b < cap ? b : cap);
-}
+unsigned tt_grid(long long total) { return (unsigned)uz_grid_cap((total + TT_THREADS - 1) / TT_THREADS, 8); }
 
 }  // namespace
 
@@ -152,9 +149,9 @@ extern "C" int uz_flip_views(const uz_tta_desc* d, const float* x, float* const*
   const long long total = (long long)d->N * d->C * d->H * d->W;
   for (int k = 0; k < v.V; ++k) {
     UZ_REQUIRE(out[k] != nullptr && ((uintptr_t)out[k] & 3) == 0, "uz_flip_views: view %d is null or misaligned", k);
-    const uintptr_t lo = (uintptr_t)out[k], hi = lo + 4 * total, xl = (uintptr_t)x, xh = xl + 4 * total;
-    UZ_REQUIRE(!(lo < xh && xl < hi), "uz_flip_views: view %d overlaps the input", k);
-    for (int j = 0; j < k; ++j) UZ_REQUIRE(!(lo < (uintptr_t)out[j] + 4 * total && (uintptr_t)out[j] < hi), "uz_flip_views: views %d and %d overlap", j, k);
+    const UzRange view = uz_range(out[k], 4 * total);
+    UZ_REQUIRE(!uz_overlap(view, uz_range(x, 4 * total)), "uz_flip_views: view %d overlaps the input", k);
+    for (int j = 0; j < k; ++j) UZ_REQUIRE(!uz_overlap(view, uz_range(out[j], 4 * total)), "uz_flip_views: views %d and %d overlap", j, k);
     v.dst[k] = out[k];
   }
   hipLaunchKernelGGL(tta_flip_kernel, dim3(tt_grid(total)), dim3(TT_THREADS), 0, static_cast<hipStream_t>(stream), v, x, total, d->H, d->W);
@@ -171,8 +168,7 @@ extern "C" int uz_tta_merge(const uz_tta_desc* d, const void* const* logits, flo
   const long long total = (long long)d->N * d->C * d->H * d->W, esz = d->dtype == UZ_F32 ? 4 : 2;
   for (int k = 0; k < v.V; ++k) {
     UZ_REQUIRE(logits[k] != nullptr && ((uintptr_t)logits[k] & (esz - 1)) == 0, "uz_tta_merge: view %d is null or misaligned", k);
-    const uintptr_t lo = (uintptr_t)logits[k], hi = lo + esz * total, pl = (uintptr_t)prob, ph = pl + 4 * total;
-    UZ_REQUIRE(!(lo < ph && pl < hi), "uz_tta_merge: view %d overlaps prob", k);
+    UZ_REQUIRE(!uz_overlap(uz_range(logits[k], esz * total), uz_range(prob, 4 * total)), "uz_tta_merge: view %d overlaps prob", k);
     v.src[k] = logits[k];
   }
   const bool cls = d->mode == UZ_POST_CLASS;

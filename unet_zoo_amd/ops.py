@@ -1703,9 +1703,7 @@ def augment_params(desc: "L.AugmentDesc", u: torch.Tensor, params: torch.Tensor)
 
 def augment_grid(desc: "L.AugmentDesc") -> tuple:
     """(workgroups, units) of the uz_augment_apply launch for this descriptor: units > workgroups means workgroups walk"""
-    units = ctypes.c_int(0)
-    grid = L.check_count(L.load().uz_augment_grid(byref(desc), byref(units)), "uz_augment_grid")
-    return grid, units.value
+    return L._desc_grid("uz_augment_grid", desc)
 
 
 def augment_apply(desc: "L.AugmentDesc", image: torch.Tensor, mask: Optional[torch.Tensor], params: torch.Tensor,
@@ -1726,7 +1724,7 @@ def augment_apply(desc: "L.AugmentDesc", image: torch.Tensor, mask: Optional[tor
 # ---- PatchSampler: foreground index of a device pool, patch coordinates from draws, the patches (uz_patch.hip) ----------------
 def patch_index_bytes(desc: "L.PatchDesc") -> int:
     """bytes of the [M][P][H + 1] int32 foreground index of this pool (0 without a mask)"""
-    return L.check_count(L.load().uz_patch_index_bytes(byref(desc)), "uz_patch_index_bytes")
+    return L._desc_bytes("uz_patch_index_bytes", desc)
 
 
 def patch_index(desc: "L.PatchDesc", mask: torch.Tensor, index: torch.Tensor) -> None:
@@ -1757,9 +1755,7 @@ def patch_draw(desc: "L.PatchDesc", u: torch.Tensor, indices: Optional[torch.Ten
 
 def patch_cut_grid(desc: "L.PatchDesc") -> tuple:
     """(workgroups, units) of the uz_patch_cut launch for this descriptor: units > workgroups means workgroups walk"""
-    units = ctypes.c_int(0)
-    grid = L.check_count(L.load().uz_patch_cut_grid(byref(desc), byref(units)), "uz_patch_cut_grid")
-    return grid, units.value
+    return L._desc_grid("uz_patch_cut_grid", desc)
 
 
 def patch_cut(desc: "L.PatchDesc", image: torch.Tensor, mask: Optional[torch.Tensor], coords: torch.Tensor,
