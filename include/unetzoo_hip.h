@@ -874,8 +874,8 @@ int uz_region_loss(const uz_region_desc* d, const uz_region_item* items, float* 
 #define UZ_CLASS_MAX_K 32
 #define UZ_CLASS_REDUCE_BATCH 0
 #define UZ_CLASS_REDUCE_IMAGE 1
-/* one output map of a composed loss (uz_class_loss, uz_boundary_loss, uz_lovasz_loss, uz_cldice_loss): the four item
- * names are one type */
+/* one output map of a composed loss (uz_class_loss, uz_boundary_loss, uz_lovasz_loss, uz_cldice_loss, uz_hardpixel_loss): the five
+ * item names are one type */
 typedef struct uz_map_item {
   const float* logits;
   float* dlogits; /* nullable; in: the base loss's gradient where there is one, out: the combined one */
@@ -1445,6 +1445,70 @@ int uz_cldice_loss(const uz_cldice_desc* d, const uz_cldice_item* items, const v
                    const float* scales /* device: weight, base_scale */, const float* base_loss /* device */,
                    float* out /* 2 */, float* probs /* N C H W, an output */, float* skeleton /* N C H W, an output */,
                    float* target_skeleton /* N C H W, an output */, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Hard-pixel mining -- top-k cross-entropy (nnU-Net's DC_and_topk), OHEM cross-entropy (keep the pixels whose true-class
+ * probability is below max_prob, and min_kept at least) and focal loss (Lin et al., ICCV 2017) -- on top of a base loss
+ * whose value and gradients exist already: an exact k-th-largest selection per segment, an MSB-first radix select over the
+ * bit patterns of the per-pixel losses.  uz_hardpixel_loss.hip
+ * A segment is a list of valid pixels, each with a plain loss l >= 0 and a true-class probability p_t = exp(-l).
+ * UZ_HARDPIXEL_CLASS : logits (N, C, H, W) fp32 with C = K classes, target (N, H, W) int32 labels y;
+ *   l = logsumexp_K(x) - x_y in fp32 with the maximum subtracted.  A pixel whose label is ignore_index or outside [0, K) is
+ *   in no segment and gets zero gradient on all K logits.  No class weights and no label smoothing enter: the base's.
+ * UZ_HARDPIXEL_BINARY: logits and target (N, C, H, W) fp32; b = target > 0.5, s = +1 where b else -1, l = softplus(-s x);
+ *   every element is valid.
+ * Focal modulation: f = (1 - p_t)^gamma l with gamma = 0 or gamma >= 1 (in (0, 1) the factor (1 - p_t)^(gamma - 1) of the
+ *   derivative is unbounded at p_t -> 1).  f increases with l, so selecting on f and on l keep the same pixels.
+ *   df/dl = (1 - p_t)^gamma + gamma (1 - p_t)^(gamma - 1) p_t l, exactly 1 at gamma = 0;
+ *   dl/dx_c = p_c - [c == y] (class), dl/dx = -s (1 - p_t) (binary).
+ * Segments: per_image = 0: one per output map over the whole batch; 1: one per image (binary: all C channels of the image).
+ * Kept count of a segment with n valid pixels: k = clamp(max(min_kept, ceil(keep n)), 1, n), the product keep n taken in
+ *   fp32 (one rounding: keep = 0.1f of n = 1000 is 100); with max_prob > 0, c = #{p_t < max_prob} counted on the plain
+ *   l > -log(max_prob) (the threshold rounded to fp32), otherwise c = 0; m = max(k, c).  n = 0: the segment adds 0 and has
+ *   zero gradient.
+ * Value: tau = the m-th largest f of the segment, n_above = #{f > tau}, n_tie = #{f == tau};
+ *   V_seg = (sum_{f > tau} f + (m - n_above) tau) / m;   V = the mean of V_seg over the segments of the map with n > 0.
+ * Gradient: a pixel with f > tau weighs 1 / m, one with f == tau weighs (m - n_above) / (n_tie m), every other 0: a
+ *   subgradient of the top-m sum that does not depend on position or arrival order; without ties torch.topk's gradient.
+ * scales = {weight, base_scale} and base_loss are ON THE DEVICE, as for uz_lovasz_loss:
+ *   out[0] = base_scale * base_loss + weight * sum_m items[m].weight * V_m;   out[1] = V of map main_item
+ *   items[m].dlogits (nullable): dl <- base_scale * dl + weight * items[m].weight * dV/dx, in place.
+ * losses is the f of map main_item in the map's own layout ((N, C, H, W) binary, (N, H, W) class; 0 at a pixel in no
+ * segment), selection (segments, 4) int32 of map main_item: m, n_above, n_tie and the bit pattern of tau; both OUTPUTS.
+ * One call is 10 launches whatever n_items, the data and the gradient buffers are: loss (with the first digit's counts),
+ * pick, 3 x (hist, pick) with 8-bit digits, grad (which also forms the float64 sums of the kept f per unit), finalize.  A
+ * unit is (segment, chunk), a chunk 2048 t consecutive elements of a segment with t the smallest integer that leaves at
+ * most 256 chunks a segment.  No allocation, no memset, no host read, no float atomics, no waiting between workgroups;
+ * integer counts and float64 sums per unit in a fixed order: two calls on the same inputs give the same bits, and so does a
+ * call with max_workgroups set.  The workspace: 4 bytes per element of every map's f, and per unit 1024 bytes of digit
+ * counts + 8 bytes of n and c + 8 bytes of sum, and 32 bytes per segment, each of the five buffers on a 16-byte boundary.
+ * uz_hardpixel_grid returns the workgroups of the passes over units and (units, nullable) the units they share out:
+ * units > workgroups means workgroups walk.
+ * UZ_EINVAL before any launch: the cases of uz_lovasz_loss (a segment longer than 2^24 here), more than 2^16 segments in
+ * the call (n_items N with per_image), keep outside (0, 1],
+ * min_kept < 0, max_prob outside {0} U (0, 1), gamma negative, not finite or in (0, 1), max_workgroups < 0. */
+#define UZ_HARDPIXEL_BINARY 0
+#define UZ_HARDPIXEL_CLASS 1
+typedef uz_map_item uz_hardpixel_item;
+typedef struct uz_hardpixel_desc {
+  int mode; /* UZ_HARDPIXEL_BINARY / UZ_HARDPIXEL_CLASS */
+  int n_items;
+  int N, C, H, W;     /* C: channels (binary) or classes K (class mode) */
+  int per_image;      /* 0: one segment per map over the whole batch */
+  int ignore_index;   /* class mode */
+  int main_item;
+  float keep;         /* (0, 1] */
+  int min_kept;       /* >= 0 */
+  float max_prob;     /* 0 = off, else in (0, 1) */
+  float gamma;        /* 0 or >= 1 */
+  int max_workgroups; /* 0: the plan's own grid; > 0: cap it, as in uz_confusion_desc */
+} uz_hardpixel_desc;
+long long uz_hardpixel_workspace_bytes(const uz_hardpixel_desc* d); /* < 0: refused */
+int uz_hardpixel_grid(const uz_hardpixel_desc* d, int* units /* nullable */);
+int uz_hardpixel_loss(const uz_hardpixel_desc* d, const uz_hardpixel_item* items, const void* target,
+                      const float* scales /* device: weight, base_scale */, const float* base_loss /* device */,
+                      float* out /* 2 */, float* losses /* an output */, int* selection /* segments * 4, an output */,
+                      void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Mask post-processing, per (image, plane), every result an integer that scipy.ndimage gives too.  uz_postproc.hip

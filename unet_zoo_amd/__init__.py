@@ -11,6 +11,7 @@ from .evalstep import GraphedEval
 from .loss import MulticlassLoss, RegionLoss
 from .boundary import BoundaryLoss
 from .lovasz import LovaszLoss
+from .hardpixel import HardPixelLoss
 from .cldice import ClDiceLoss
 from .augment import GpuAugment
 from .patches import PatchSampler
@@ -24,6 +25,6 @@ from .config import Config, load_config
 
 __version__ = "0.1.0"
 __all__ = ["create_model", "list_models", "get_model_config", "hip_models", "set_default_dtype",
-           "get_default_dtype", "GraphedStep", "GraphedEval", "RegionLoss", "MulticlassLoss", "BoundaryLoss", "LovaszLoss", "ClDiceLoss", "GpuAugment", "PatchSampler", "LrSchedule", "SurfaceMetrics", "ConfusionMetrics",
+           "get_default_dtype", "GraphedStep", "GraphedEval", "RegionLoss", "MulticlassLoss", "BoundaryLoss", "LovaszLoss", "ClDiceLoss", "HardPixelLoss", "GpuAugment", "PatchSampler", "LrSchedule", "SurfaceMetrics", "ConfusionMetrics",
            "MaskPostprocess", "GraphedPredict", "SlidingWindowPredict",
            "Config", "load_config"]

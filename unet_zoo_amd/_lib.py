@@ -65,6 +65,7 @@ EXPORTS = (
     "uz_boundary_workspace_bytes", "uz_boundary_grid", "uz_boundary_loss",
     "uz_lovasz_workspace_bytes", "uz_lovasz_grid", "uz_lovasz_loss",
     "uz_cldice_workspace_bytes", "uz_cldice_grid", "uz_cldice_loss",
+    "uz_hardpixel_workspace_bytes", "uz_hardpixel_grid", "uz_hardpixel_loss",
     "uz_postproc_workspace_bytes", "uz_postproc_grid", "uz_postproc",
     "uz_tta_num_views", "uz_flip_views", "uz_tta_merge", "uz_mask_decide",
     "uz_tile_plan", "uz_tile_gather", "uz_tile_blend",
@@ -177,12 +178,12 @@ CLASS_REDUCE_BATCH, CLASS_REDUCE_IMAGE = 0, 1
 
 
 class MapItem(Structure):
-    """uz_map_item: one output map of a composed loss call; uz_class_item, uz_boundary_item, uz_lovasz_item and
-    uz_cldice_item are this one type"""
+    """uz_map_item: one output map of a composed loss call; uz_class_item, uz_boundary_item, uz_lovasz_item,
+    uz_cldice_item and uz_hardpixel_item are this one type"""
     _fields_ = [("logits", c_void_p), ("dlogits", c_void_p), ("weight", c_float)]
 
 
-ClassItem = BoundaryItem = LovaszItem = ClDiceItem = MapItem
+ClassItem = BoundaryItem = LovaszItem = ClDiceItem = HardPixelItem = MapItem
 
 
 class ClassDesc(Structure):
@@ -278,6 +279,20 @@ class ClDiceDesc(Structure):
     """uz_cldice_desc"""
     _fields_ = [(n, c_int) for n in ("mode", "n_items", "N", "C", "H", "W", "per_image", "include_background", "ignore_index",
                                      "iterations")] + [("smooth", c_float), ("main_item", c_int)]
+
+
+HARDPIXEL_BINARY, HARDPIXEL_CLASS = 0, 1
+HARDPIXEL_MAX_SEGMENT = 1 << 24
+HARDPIXEL_MAX_ELEMENTS = 1 << 28
+HARDPIXEL_MAX_SEGMENTS = 1 << 16     # segments of a call: output maps x images with per_image
+HARDPIXEL_MIN_KEEP = 2.0 ** -126     # the smallest normal fp32: what HardPixelLoss.ohem sets `keep` to
+HARDPIXEL_TILE, HARDPIXEL_MAX_ROWS = 2048, 256      # a chunk is TILE * t elements, at most MAX_ROWS chunks a segment
+
+
+class HardPixelDesc(Structure):
+    """uz_hardpixel_desc"""
+    _fields_ = [(n, c_int) for n in ("mode", "n_items", "N", "C", "H", "W", "per_image", "ignore_index", "main_item")] \
+        + [("keep", c_float), ("min_kept", c_int), ("max_prob", c_float), ("gamma", c_float), ("max_workgroups", c_int)]
 
 
 POST_BINARY, POST_CLASS = 0, 1
@@ -525,6 +540,9 @@ def load():
     lib.uz_cldice_workspace_bytes.argtypes = [POINTER(ClDiceDesc)]
     lib.uz_cldice_grid.argtypes = [POINTER(ClDiceDesc), POINTER(c_int)]
     lib.uz_cldice_loss.argtypes = [POINTER(ClDiceDesc), POINTER(ClDiceItem), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.uz_hardpixel_workspace_bytes.argtypes = [POINTER(HardPixelDesc)]
+    lib.uz_hardpixel_grid.argtypes = [POINTER(HardPixelDesc), POINTER(c_int)]
+    lib.uz_hardpixel_loss.argtypes = [POINTER(HardPixelDesc), POINTER(HardPixelItem), vp, vp, vp, vp, vp, vp, vp, vp]
     lib.uz_postproc_workspace_bytes.argtypes = [POINTER(PostprocDesc)]
     lib.uz_postproc_grid.argtypes = [POINTER(PostprocDesc), POINTER(c_int)]
     lib.uz_postproc.argtypes = [POINTER(PostprocDesc), vp, vp, vp, vp, vp, vp, vp, vp]
@@ -701,6 +719,29 @@ def cldice_loss(desc: "ClDiceDesc", items, target: torch.Tensor, scales: torch.T
     check(load().uz_cldice_loss(ctypes.byref(desc), items, target.data_ptr(), scales.data_ptr(), base_loss.data_ptr(),
                                 out2.data_ptr(), probs.data_ptr(), skeleton.data_ptr(), target_skeleton.data_ptr(),
                                 workspace.data_ptr(), stream_ptr()), "uz_cldice_loss")
+
+
+def hardpixel_workspace_bytes(desc: "HardPixelDesc") -> int:
+    """uz_hardpixel_workspace_bytes(): bytes of workspace a uz_hardpixel_loss call with this descriptor needs"""
+    return _desc_bytes("uz_hardpixel_workspace_bytes", desc)
+
+
+def hardpixel_grid(desc: "HardPixelDesc") -> tuple:
+    """uz_hardpixel_grid(): (workgroups, units) of the passes over (segment, chunk) units of uz_hardpixel_loss for this
+    descriptor"""
+    return _desc_grid("uz_hardpixel_grid", desc)
+
+
+def hardpixel_loss(desc: "HardPixelDesc", items, target: torch.Tensor, scales: torch.Tensor, base_loss: torch.Tensor,
+                   out2: torch.Tensor, losses: torch.Tensor, selection: torch.Tensor, workspace: torch.Tensor) -> None:
+    """uz_hardpixel_loss() on the current stream: `items` is a ctypes array of HardPixelItem (a HOST table, copied into the
+    kernel arguments), scales the (weight, base_scale) pair and base_loss the base criterion's value ON THE DEVICE, out2 a
+    2-element fp32 device tensor (loss, V of the main map), losses (fp32, the map's layout) and selection (int32,
+    (segments, 4)) the outputs of the main map.  10 launches, no allocation, no host read.  Every call of the loss goes
+    through here."""
+    check(load().uz_hardpixel_loss(ctypes.byref(desc), items, target.data_ptr(), scales.data_ptr(), base_loss.data_ptr(),
+                                   out2.data_ptr(), losses.data_ptr(), selection.data_ptr(), workspace.data_ptr(), stream_ptr()),
+          "uz_hardpixel_loss")
 
 
 def postproc_workspace_bytes(desc: "PostprocDesc") -> int:

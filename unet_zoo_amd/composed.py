@@ -1,5 +1,5 @@
-"""What the criteria composed on a base loss share (``BoundaryLoss``: boundary.py, ``LovaszLoss``: lovasz.py, ``ClDiceLoss``: cldice.py): ``loss =
-base_scale * base + weight * term`` with the base's launch first and ONE launch sequence of the term's kernels on the gradients
+"""What the criteria composed on a base loss share (``BoundaryLoss``: boundary.py, ``LovaszLoss``: lovasz.py, ``ClDiceLoss``:
+cldice.py, ``HardPixelLoss``: hardpixel.py): ``loss = base_scale * base + weight * term`` with the base's launch first and ONE launch sequence of the term's kernels on the gradients
 the base wrote; ``weight`` and ``base_scale`` in two device scalars that the kernels read, so that ``set_weights`` reaches a
 captured graph without a new capture.  The three forms are ``FusedCriterion``'s (criterion.py).
 

@@ -47,7 +47,7 @@ static inline int uz_grid_cap(long long units, int per_cu) {
   return (int)(units < cap ? units : cap);
 }
 
-// ---- the item table of the composed losses (uz_boundary_loss, uz_lovasz_loss, uz_cldice_loss) ----------------------------
+// ---- the item table of the composed losses (uz_boundary_loss, uz_lovasz_loss, uz_cldice_loss, uz_hardpixel_loss) ---------
 // Checks every item, appends its logits to ins[] and its dlogits (where given) to outs[], notes whether any map takes a
 // gradient, and fills the kernel-argument table tab[UZ_CLASS_MAX_ITEMS], padded with item 0.
 static inline int uz_map_items(const char* who, const uz_map_item* items, int n_items, long long map_bytes, UzRange* ins, int* n_in,

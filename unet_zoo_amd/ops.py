@@ -1924,6 +1924,36 @@ def cldice_loss(desc: "L.ClDiceDesc", items, target: torch.Tensor, scales: torch
         L.cldice_loss(desc, items, target, scales, base_loss, out2, probs, skeleton, target_skeleton, workspace)
 
 
+# ---- HardPixelLoss: top-k / OHEM / focal pixel mining, an MSB-first radix select of the pixel losses (uz_hardpixel_loss.hip) ----
+def hardpixel_grid(desc: "L.HardPixelDesc") -> tuple:
+    """(workgroups, units) of the passes over (segment, chunk) units of uz_hardpixel_loss for this descriptor: units >
+    workgroups means workgroups walk"""
+    return L.hardpixel_grid(desc)
+
+
+def hardpixel_loss(desc: "L.HardPixelDesc", items, target: torch.Tensor, scales: torch.Tensor, base_loss: torch.Tensor,
+                   out2: torch.Tensor, losses: torch.Tensor, selection: torch.Tensor, workspace: torch.Tensor) -> None:
+    """out2 = (base_scale * base_loss + weight * sum_m ow_m V_m, V_main), losses (the f of the main map, in its layout) and
+    selection ((segments, 4): m, n_above, n_tie, bits of tau) <- the maps of `items` (fp32, (N, C, H, W)) against target:
+    fp32 (N, C, H, W) masks (UZ_HARDPIXEL_BINARY) or int32 (N, H, W) labels (UZ_HARDPIXEL_CLASS); the gradient buffers of
+    `items` are rewritten in place; 10 launches"""
+    L.require_cuda(target, scales, base_loss, out2, losses, selection, workspace)
+    for t in (target, scales, base_loss, out2, losses, selection, workspace):
+        assert t.is_contiguous()
+    cls = desc.mode == L.HARDPIXEL_CLASS
+    fshape = (desc.N, desc.H, desc.W) if cls else (desc.N, desc.C, desc.H, desc.W)
+    assert scales.dtype == base_loss.dtype == out2.dtype == losses.dtype == torch.float32 and selection.dtype == torch.int32
+    assert target.dtype == (torch.int32 if cls else torch.float32)
+    assert tuple(target.shape) == fshape and tuple(losses.shape) == fshape
+    assert scales.numel() == 2 and out2.numel() == 2 and base_loss.numel() == 1
+    assert tuple(selection.shape) == (desc.N if desc.per_image else 1, 4)
+    elems = desc.n_items * desc.N * desc.C * desc.H * desc.W
+    # per element of every map: logits read by the loss pass 4 and (where kept) by the gradient pass, the gradient read and
+    # written 8; per f value: written 4, read by three hist passes (mostly skipped after the first) and the gradient pass 8
+    with _Timed("hardpixel_loss", 0.0, 4.0 * target.numel() + 12.0 * elems + 12.0 * desc.n_items * losses.numel()):
+        L.hardpixel_loss(desc, items, target, scales, base_loss, out2, losses, selection, workspace)
+
+
 # ---- MaskPostprocess / GraphedPredict: components, hole filling, flip TTA (uz_postproc.hip, uz_tta.hip) -----------------------
 def postproc_grid(desc: "L.PostprocDesc") -> tuple:
     """(workgroups, units) of the per-unit launches of uz_postproc for this descriptor: units > workgroups means workgroups
